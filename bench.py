@@ -16,9 +16,12 @@ communication); every step each rank polygonizes its range and the ranks exchang
 collective: MPUs are independent, no halo).  value = 256^3 / max-over-ranks step time.
 `--scaling weak` instead gives every rank its own grid (frame r of the animated tree).
 
-Output: one JSON line on rank 0 (the driver's contract) with `roofline` for the dominant
-kernel (hipEvent-timed on the library's stream) and `cpu_baseline` (the oracle, rank 0,
-N=1 only).
+Output: one JSON line on rank 0 (the driver's contract).  A plain run sets up, warms up,
+times the K steps and prints the line (`ms_per_step`, `value`, the workload and the mesh
+counts); `--dump-outputs DIR` also writes the last timed step's mesh as DIR/<name>.npy.
+`--full` adds what takes GPU or CPU runs of its own: `roofline` for the dominant kernel
+(hipEvent-timed on the library's stream), the per-kernel times, the single-polygonization
+latency and blocking Polygonize timings, and `cpu_baseline` (the oracle, rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -64,6 +67,8 @@ METRIC = "Mcells/sec polygonized, 256^3 grid 32-prim BlobTree, at 1/2/4/8 MI355X
 # other configs are parity / scaling rehearsals, labelled by their own workload
 METRIC_OTHER = "Mcells/sec polygonized, {n}^3 grid {p}-prim BlobTree ({config}), at {g} MI355X"
 NOFMA_PEAK_TOPS = 78.6  # fp32 VALU lane-ops without FMA (-ffp-contract=off): 256 CU x 4 SIMD-32 x 32 lanes x 2.4 GHz
+DUMP_BYTES_MAX = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all (C3's mesh: 25.5 MB)
+DUMP_SEED = 20240  # of the row sample a larger mesh is cut down to
 
 
 def spawn_ranks(n: int) -> int:
@@ -331,6 +336,45 @@ def blocking_contract(polys, config="C2", reps=24):
     return res
 
 
+def dump_outputs(path, mesh, prefix="", budget=DUMP_BYTES_MAX):
+    """--dump-outputs: the compact mesh of the last timed step (gpu.Mesh, what a caller of the
+    timed path downloads) as <path>/<prefix><name>.npy: the fp32 arrays as they are, the
+    integer ones (triangles' vertex ids, per-MPU offsets) as float64, which holds them exactly.
+    Past `budget` bytes in all, every array keeps the same fraction of its rows, chosen by a
+    fixed seed (arrays of equal length keep the same rows), in their order.
+
+    Every file holds finite numbers only, so that two dumps compare by value.  The mesh itself
+    need not: where the field's gradient is zero the reference normalises 0 x rsqrt(0), and the
+    normal is NaN there as in the reference (C3: 179 of 339,820 vertices, on the lattice's
+    border).  Such an element is written as 0, and vertex_nonfinite.npy says so: one row per
+    vertex, one column per component of pos, nrm and col in that order (V x 9, float32), 0 for
+    a finite element, 1 NaN, 2 +inf, 3 -inf.  Its shape depends on the vertex count alone, and
+    with it the three vertex files are the arrays the caller receives."""
+    kinds = [np.where(np.isnan(a), 1, np.where(np.isposinf(a), 2, np.where(np.isneginf(a), 3, 0)))
+             for a in (mesh.pos, mesh.nrm, mesh.col)]
+    arrays = {"pos": mesh.pos, "nrm": mesh.nrm, "col": mesh.col,
+              "vertex_nonfinite": np.concatenate(kinds, axis=1).astype(np.float32),
+              "tris": mesh.tris.astype(np.float64),
+              "vertex_offsets": mesh.vertex_offsets.astype(np.float64),
+              "triangle_offsets": mesh.triangle_offsets.astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        rows = len(a)
+        if total > budget:
+            keep = int(rows * budget / total)
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))]
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "rows_of": rows}
+        if name in ("pos", "nrm", "col"):
+            bad = ~np.isfinite(a)
+            entry["nonfinite"] = int(bad.sum())
+            a = np.where(bad, np.float32(0), a)
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), a)
+        written[prefix + name] = entry
+    return written
+
+
 class Engine:
     """One device context over the rank's MPU range [begin, end) (parts == 1), or a group of
     `parts` cost-balanced sub-ranges on as many streams of the device."""
@@ -450,9 +494,18 @@ def main():
     ap.add_argument("--rebalance", type=int, default=2,
                     help="strong scaling: rebalance the cost split this many times from the ranks' measured step "
                          "times before the timed steps (gpu.rebalance)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the roofline passes "
+                         "(per-kernel spans, hipEvent times, the kernels alone on the device), the "
+                         "single-polygonization latency, the blocking Polygonize timings and the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the mesh the last timed step produced (what a caller downloads: positions, "
+                         "normals, colours, triangles, per-MPU offsets) as DIR/<name>.npy, finite numbers only: "
+                         "an element that is not (a NaN normal at a zero gradient) is written as 0 and marked "
+                         "in DIR/vertex_nonfinite.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the single-polygonization latency and the blocking C2 Polygonize timing")
+                    help="--full: skip the single-polygonization latency and the blocking C2 Polygonize timing")
     ap.add_argument("--no-cull", action="store_true", help="disable exact primitive culling")
     ap.add_argument("--jit", type=int, default=None, choices=[0, 1, 2, 3],
                     help="0 interpreter, 1 kernels specialised per tree structure (default), 2 + parameters baked "
@@ -666,6 +719,93 @@ def main():
         if not ok:
             sys.exit(f"bench.py rank {grp.rank}: parts {counts} do not add up to the full grid {check['full']}")
 
+    # --dump-outputs: the mesh of the last timed step (step K-1 ran on engine (K-1) mod E), this
+    # rank's part of it when the grid is split over ranks
+    dumped = None
+    if args.dump_outputs:
+        last = engines[(args.steps - 1) % neng]
+        dumped = dump_outputs(args.dump_outputs, (last.p if last.p is not None else last.obj).download(),
+                              prefix=f"rank{grp.rank}_" if grp.world > 1 else "",
+                              budget=DUMP_BYTES_MAX // grp.world)
+
+    # k_front (PSGPU_OPT_FRONT): k_precheck's and k_mpu's waves are the S1 and S2 blocks of ONE launch
+    front = bool(mine.launchFlags & gpu.LAUNCH_FRONT)
+    # what the timed steps ran, per engine: 0 interpreter, 1 structure kernels, 2 baked kernels
+    tiers_timed = [e.jit_tier() for e in engines]
+    if args.jit and not jit_on:
+        kernels_label = "interpreter (jit unavailable)"
+    elif args.jit == gpu.JIT_TIERED:
+        kernels_label = ("jit-tiered: baked tier" if timed_jit == gpu.JIT_BAKED
+                         else "jit-tiered: structure tier (the baked kernels were not ready)")
+    else:
+        kernels_label = ["interpreter", "jit-structure", "jit-baked"][args.jit]
+    out = {
+        "metric": METRIC if args.config == "C3" else METRIC_OTHER.format(
+            n=N, p=model.ct_prims, config=args.config, g=grp.world),
+        "value": round(value, 2),
+        "unit": "Mcells/s",
+        "n_gpus": grp.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": f"synthetic: {args.config} BlobTree from std::mt19937(42) as in the reference probe (SURVEY.md §6, §8(d))",
+        "config": {"workload": (f"{args.config}: {model.ct_prims}-prim/{model.ct_ops}-op BlobTree, {N}^3 cells, "
+                                f"{n_mpus} MPUs")
+                               + (" split over the ranks (C4)" if full is not None else "")
+                               + (", a grid per rank (frame = rank)" if scaling == "weak" and grp.world > 1 else ""),
+                   "grid": N, "mpus": n_mpus, "prims": model.ct_prims, "ops": model.ct_ops,
+                   "parallelism": f"{scaling}-{grp.world}gpu", "engines_per_gpu": neng, "parts_per_engine": nparts,
+                   "streams_per_gpu": neng * nparts,
+                   "persistent_blocks_per_cu": [args.vertex_blocks or (8 if neng > 1 else 16),
+                                                args.finish_blocks or (4 if neng > 1 else 8)],
+                   "grids": "k_vertex / k_finish: a wave per batch of the last run's vertices + 1/8, at most "
+                            "the persistent grids" if os.environ.get("PSGPU_GRID_FIT", "1") != "0" else "persistent",
+                   "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
+                   "step": "one complete polygonization of the rank's MPU range (S1-S6: k_precheck + k_mpu, "
+                           "one launch when launch_flags says k_front, then k_vertex + k_finish, or k_surface); "
+                           "steps alternate between the engines and are queued without host sync",
+                   "launch_flags": {"k_front": front, "tree_split": bool(mine.launchFlags & gpu.LAUNCH_TREE_SPLIT),
+                                    "k_surface": bool(mine.launchFlags & gpu.LAUNCH_SURFACE)},
+                   "mpu_range_rank0": [begin, end] if grp.rank == 0 else None,
+                   "exchange": exchange, "culling": not args.no_cull, "tree_split": args.tree_split,
+                   "fused_surface": ("auto: k_vertex + k_finish as one launch when both take their quad layouts"
+                                     if args.tree_split and os.environ.get("PSGPU_FUSED_SURFACE", "2") != "0"
+                                     else "off"),
+                   "kernels": kernels_label, "tiers": tiers_timed, "set_model_s": round(t_model, 4),
+                   "jit_ready_s": round(t_jit, 3),
+                   "host_enqueue_ms": round((t_enq - t0) * 1e3, 4)},
+        "mesh": {"vertices": info.ctVertices, "triangles": info.ctTriangles, "passed_s1": info.ctPassedPrecheck,
+                 "surface_mpus": info.ctSurfaceMPUs, "field_mpus": info.ctFieldMPUs, "per_rank": counts},
+        "hbm_gbs_algorithmic": round((mine.ctVertices * 36 + mine.ctTriangles * 12) / (ms_step * 1e-3) / 1e9, 2),
+    }
+    if tier:
+        out["config"]["tiered"] = tier
+    if check:
+        out["check"] = check
+    if split_log:
+        out["config"]["split"] = dict(split_log, note="cost split (psgpu_split_costs) refined from all-gathered "
+                                      "measured step times before the timed steps (gpu.rebalance)")
+    if dumped:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                          "note": "the mesh of the last timed step" + (", rank 0's part" if grp.world > 1 else "")}
+
+    def emit_and_close():
+        if grp.rank == 0:
+            print(json.dumps(out), file=json_out, flush=True)
+        for e in engines:
+            e.close()
+        if grp.dist:
+            grp.dist.destroy_process_group()
+        poly.close()
+
+    if not args.full:  # a plain run ends here: everything below takes GPU runs of its own
+        emit_and_close()
+        return
+
     # roofline pass 1: the timed steps again, identically (K steps alternating between the
     # engines, queued without host sync), with every launch recording its kernels' spans on
     # the device clock (first wave start -> last wave end: one 64-bit atomic min / max per
@@ -684,10 +824,7 @@ def main():
         e.set_option(gpu.OPT_SPANS, 0)
     launches = len(sp)
     kt = {k: float(sp[:, i].mean()) for i, k in enumerate(gpu.STAMP_KERNELS)}
-    # k_front (PSGPU_OPT_FRONT): k_precheck's and k_mpu's waves are the S1 and S2 blocks of ONE
-    # launch; its span is theirs together
-    front = bool(mine.launchFlags & gpu.LAUNCH_FRONT)
-    if front:
+    if front:  # its span is k_precheck's and k_mpu's together
         kt["k_front"] = float(((np.maximum(spr[:, 0, 1], spr[:, 1, 1]) - np.minimum(spr[:, 0, 0], spr[:, 1, 0]))
                                * 1e-5).mean())
     fmpus = sum(e.local_info().ctFieldMPUs for e in engines) / neng * launches / nparts
@@ -867,70 +1004,11 @@ def main():
                             "reference-priced per-launch figure of the dominant kernel is 'per_launch'"}
     roof = step if step else dict(lk)
     roof["per_launch"] = lk
+    out["roofline"] = roof
+    out["kernel_ms_per_launch"] = {k: round(v, 4) for k, v in kt.items()}
+    out["kernel_ms_per_launch_hipevent"] = {k: round(v, 4) for k, v in ev_ms.items()}
+    out["kernel_ms_per_launch_isolated"] = {k: round(v, 4) for k, v in solo.items()}
 
-    # what the timed steps ran, per engine: 0 interpreter, 1 structure kernels, 2 baked kernels
-    tiers_timed = [e.jit_tier() for e in engines]
-    if args.jit and not jit_on:
-        kernels_label = "interpreter (jit unavailable)"
-    elif args.jit == gpu.JIT_TIERED:
-        kernels_label = ("jit-tiered: baked tier" if timed_jit == gpu.JIT_BAKED
-                         else "jit-tiered: structure tier (the baked kernels were not ready)")
-    else:
-        kernels_label = ["interpreter", "jit-structure", "jit-baked"][args.jit]
-    out = {
-        "metric": METRIC if args.config == "C3" else METRIC_OTHER.format(
-            n=N, p=model.ct_prims, config=args.config, g=grp.world),
-        "value": round(value, 2),
-        "unit": "Mcells/s",
-        "n_gpus": grp.world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": f"synthetic: {args.config} BlobTree from std::mt19937(42) as in the reference probe (SURVEY.md §6, §8(d))",
-        "config": {"workload": (f"{args.config}: {model.ct_prims}-prim/{model.ct_ops}-op BlobTree, {N}^3 cells, "
-                                f"{n_mpus} MPUs")
-                               + (" split over the ranks (C4)" if full is not None else "")
-                               + (", a grid per rank (frame = rank)" if scaling == "weak" and grp.world > 1 else ""),
-                   "grid": N, "mpus": n_mpus, "prims": model.ct_prims, "ops": model.ct_ops,
-                   "parallelism": f"{scaling}-{grp.world}gpu", "engines_per_gpu": neng, "parts_per_engine": nparts,
-                   "streams_per_gpu": neng * nparts,
-                   "persistent_blocks_per_cu": [args.vertex_blocks or (8 if neng > 1 else 16),
-                                                args.finish_blocks or (4 if neng > 1 else 8)],
-                   "grids": "k_vertex / k_finish: a wave per batch of the last run's vertices + 1/8, at most "
-                            "the persistent grids" if os.environ.get("PSGPU_GRID_FIT", "1") != "0" else "persistent",
-                   "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
-                   "step": "one complete polygonization of the rank's MPU range (S1-S6: k_precheck + k_mpu, "
-                           "one launch when launch_flags says k_front, then k_vertex + k_finish, or k_surface); "
-                           "steps alternate between the engines and are queued without host sync",
-                   "launch_flags": {"k_front": front, "tree_split": bool(mine.launchFlags & gpu.LAUNCH_TREE_SPLIT),
-                                    "k_surface": bool(mine.launchFlags & gpu.LAUNCH_SURFACE)},
-                   "mpu_range_rank0": [begin, end] if grp.rank == 0 else None,
-                   "exchange": exchange, "culling": not args.no_cull, "tree_split": args.tree_split,
-                   "fused_surface": ("auto: k_vertex + k_finish as one launch when both take their quad layouts"
-                                     if args.tree_split and os.environ.get("PSGPU_FUSED_SURFACE", "2") != "0"
-                                     else "off"),
-                   "kernels": kernels_label, "tiers": tiers_timed, "set_model_s": round(t_model, 4),
-                   "jit_ready_s": round(t_jit, 3),
-                   "host_enqueue_ms": round((t_enq - t0) * 1e3, 4)},
-        "roofline": roof,
-        "kernel_ms_per_launch": {k: round(v, 4) for k, v in kt.items()},
-        "kernel_ms_per_launch_hipevent": {k: round(v, 4) for k, v in ev_ms.items()},
-        "kernel_ms_per_launch_isolated": {k: round(v, 4) for k, v in solo.items()},
-        "mesh": {"vertices": info.ctVertices, "triangles": info.ctTriangles, "passed_s1": info.ctPassedPrecheck,
-                 "surface_mpus": info.ctSurfaceMPUs, "field_mpus": info.ctFieldMPUs, "per_rank": counts},
-        "hbm_gbs_algorithmic": round((mine.ctVertices * 36 + mine.ctTriangles * 12) / (ms_step * 1e-3) / 1e9, 2),
-    }
-    if tier:
-        out["config"]["tiered"] = tier
-    if check:
-        out["check"] = check
-    if split_log:
-        out["config"]["split"] = dict(split_log, note="cost split (psgpu_split_costs) refined from all-gathered "
-                                      "measured step times before the timed steps (gpu.rebalance)")
     if grp.rank == 0 and grp.world == 1 and not args.no_extras:
         lat = latency_single(engines[0].p if engines[0].p is not None else poly, cs)
         out["latency_ms_single"] = {"median": lat[0], "best": lat[1],
@@ -953,13 +1031,7 @@ def main():
             bg.close()
     if grp.rank == 0 and grp.world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(model, cs, N ** 3, args.config)
-    if grp.rank == 0:
-        print(json.dumps(out), file=json_out, flush=True)
-    for e in engines:
-        e.close()
-    if grp.dist:
-        grp.dist.destroy_process_group()
-    poly.close()
+    emit_and_close()
 
 
 if __name__ == "__main__":

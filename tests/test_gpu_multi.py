@@ -366,8 +366,56 @@ def _bench(args, env_extra=None, timeout=300):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_dumps_last_mesh(gpu_poly, tmp_path):
+    """A plain run times its steps and prints the line, without the legs of --full; what
+    --dump-outputs writes is the mesh a caller downloads after one polygonization of C3."""
+    d = tmp_path / "dump"
+    out = _bench(["--gpus", "1", "--steps", "6", "--warmup", "1", "--dump-outputs", str(d)], timeout=120)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "mesh"):
+        assert k in out, k
+    assert out["steps"] == 6 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["value"] == pytest.approx(256 ** 3 / (out["ms_per_step"] * 1e-3) / 1e6, rel=1e-2)
+    for k in ("roofline", "cpu_baseline", "latency_ms_single", "blocking_polygonize_mpus",
+              "kernel_ms_per_launch", "kernel_ms_per_launch_hipevent", "kernel_ms_per_launch_isolated"):
+        assert k not in out, k
+    model, cs, _ = synth.make_config("C3")
+    gpu_poly.set_model(model)
+    gpu_poly.run(cs)
+    mesh = gpu_poly.download()
+    names = ("pos", "nrm", "col", "tris", "vertex_offsets", "triangle_offsets")
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names + ("vertex_nonfinite",))
+    assert sorted(out["outputs"]["arrays"]) == sorted(names + ("vertex_nonfinite",))
+    # one row per vertex whatever the values: 0 finite, 1 NaN, 2 +inf, 3 -inf per component of pos, nrm, col
+    nf = np.load(d / "vertex_nonfinite.npy")
+    assert nf.dtype == np.float32 and nf.shape == (len(mesh.pos), 9)
+    total = nf.nbytes
+    for n in names:
+        a = np.load(d / (n + ".npy"))
+        total += a.nbytes
+        want = getattr(mesh, n)
+        assert a.dtype == (np.float32 if want.dtype == np.float32 else np.float64), n
+        assert a.shape == want.shape and a.size > 0, n
+        assert np.isfinite(a).all(), n  # every file compares by value
+        if want.dtype != np.float32:
+            np.testing.assert_array_equal(a, want)
+            continue
+        # the file and its columns of vertex_nonfinite together are the downloaded array: finite
+        # elements bit for bit, the others (the reference's NaN normals at zero gradient) 0 and marked
+        k = 3 * ("pos", "nrm", "col").index(n)
+        bad = ~np.isfinite(want)
+        np.testing.assert_array_equal(
+            nf[:, k:k + 3], np.where(np.isnan(want), 1, np.where(np.isposinf(want), 2, np.where(np.isneginf(want), 3, 0))))
+        assert int(bad.sum()) == out["outputs"]["arrays"][n]["nonfinite"], n
+        assert not a[bad].any(), n
+        assert_bits_equal(a[~bad], want[~bad], n)
+    # positions and colours are finite; the normals are NaN exactly where the oracle's are (C3: 179 vertices)
+    assert out["outputs"]["arrays"]["pos"]["nonfinite"] == 0 and out["outputs"]["arrays"]["col"]["nonfinite"] == 0
+    assert out["outputs"]["arrays"]["nrm"]["nonfinite"] == 537
+    assert total <= 64 * 1000 * 1000
+
+
 def test_bench_contract_one_gpu():
-    out = _bench(["--steps", "5", "--warmup", "1", "--no-cpu"])
+    out = _bench(["--steps", "5", "--warmup", "1", "--full", "--no-cpu"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out, k

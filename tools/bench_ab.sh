@@ -13,7 +13,7 @@ for r in $(seq $REPS); do
     IFS='|' read -r label args envs <<< "$v"
     IFS=';' read -ra E <<< "$envs"
     f=$OUT/${label}_$r.json
-    env "${E[@]}" timeout -k 10 240 python3 bench.py --no-cpu --no-extras $args > $f 2> $OUT/${label}_$r.err || { echo "FAILED $label $r"; tail -5 $OUT/${label}_$r.err; exit 1; }
+    env "${E[@]}" timeout -k 10 240 python3 bench.py --full --no-cpu --no-extras $args > $f 2> $OUT/${label}_$r.err || { echo "FAILED $label $r"; tail -5 $OUT/${label}_$r.err; exit 1; }
     python3 -c "import json,sys;d=json.load(open('$f'));t=d['config'].get('tiered',{}).get('structure_kernels',{}).get('ms_per_step');k=d.get('kernel_ms_per_launch_isolated',{});print('$label', $r, d['ms_per_step'], 'structure_pass', t, 'isolated', ' '.join('%s=%.1f'%(a[2:],b*1e3) for a,b in k.items()))" | tee -a $OUT/ab.txt
   done
 done

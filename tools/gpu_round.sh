@@ -34,7 +34,7 @@ if [ "$2" != "notests" ]; then
   cat $OUT/smoke.log
 fi
 # the driver's command with the kernels of one tier pinned (--jit J), no CPU leg / extras
-DRV="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras"
+DRV="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-extras"
 for J in ${4:-2 1}; do
   D=$OUT/j$J
   mkdir -p $D
@@ -48,11 +48,11 @@ for J in ${4:-2 1}; do
 done
 # the bench lines, measured after the profiles so they report their traffic / VALU figures:
 # the driver's exact command first
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -20 $OUT/bench_driver.err; exit 1; }
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -20 $OUT/bench_driver.err; exit 1; }
 cat $OUT/bench_driver.json
-timeout -k 10 400 python3 bench.py --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
-timeout -k 10 300 python3 bench.py --config C5 --no-cpu --no-extras --steps 200 > $OUT/bench_c5.json 2> $OUT/bench_c5.err || { tail -20 $OUT/bench_c5.err; exit 1; }
+timeout -k 10 300 python3 bench.py --config C5 --full --no-cpu --no-extras --steps 200 > $OUT/bench_c5.json 2> $OUT/bench_c5.err || { tail -20 $OUT/bench_c5.err; exit 1; }
 cat $OUT/bench_c5.json
 [ "$3" = "nogui" ] && exit 0
 # compat mode (the GUI path): the train scene at three cell sizes, generated kernels

@@ -8,7 +8,7 @@ TAG=${1:-ic}; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --no-cpu --no-extras --steps 5 --warmup 1 $*"
+BENCH="python3 bench.py --full --no-cpu --no-extras --steps 5 --warmup 1 $*"
 i=0
 for SET in "SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES" \
            "SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_INSTS_SMEM SQ_INSTS_VALU SQ_WAVES SQC_TC_INST_REQ"; do

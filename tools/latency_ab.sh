@@ -10,7 +10,7 @@ for r in $(seq $REPS); do
     IFS='|' read -r label args envs <<< "$v"
     IFS=';' read -ra E <<< "$envs"
     f=$OUT/${label}_$r.json
-    env "${E[@]}" timeout -k 10 300 python3 bench.py --no-cpu --steps 20 --warmup 5 $args > $f 2> $OUT/${label}_$r.err || { echo "FAILED $label"; tail -5 $OUT/${label}_$r.err; exit 1; }
+    env "${E[@]}" timeout -k 10 300 python3 bench.py --full --no-cpu --steps 20 --warmup 5 $args > $f 2> $OUT/${label}_$r.err || { echo "FAILED $label"; tail -5 $OUT/${label}_$r.err; exit 1; }
     python3 -c "import json;d=json.load(open('$f'));a=d['latency_ms_single'];b=d['latency_ms_single_parts'];print('$label', $r, 'single', a['median'], a['best'], 'parts', b['median'], b['best'], 'step', d['ms_per_step'])"
   done
 done

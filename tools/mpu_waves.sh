@@ -2,6 +2,7 @@
 #   PSGPU_MPU_WAVES=<w> python -c "from parsip_amd import build; build.build(force=True)"
 # and copied to exp/lib_w<w>.so).  WAVES="1 2 4" picks the order, BENCH_ARGS adds bench flags.
 mkdir -p gpurun_out; o=gpurun_out/mw.txt; : > $o
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-kernel times read below are part of --full
 cp parsip_amd/libparsip_gpu.so exp/lib_default.so
 for w in ${WAVES:-1 2 4}; do
   cp exp/lib_w$w.so parsip_amd/libparsip_gpu.so

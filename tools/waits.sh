@@ -32,7 +32,7 @@ for V in "s|--jit 1|0" "b|--jit 2|0" "s1|--jit 1|1" "s32|--jit 1|32"; do
   for SET in "${SETS[@]}"; do
     i=$((i+1))
     PSGPU_FRONT=0 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $OUT/$name/p$i -o run -- \
-      python3 bench.py --no-cpu --no-extras --steps 5 --warmup 1 --tree-split 0 --debug $dbg $args > $OUT/$name/p$i.log 2>&1 \
+      python3 bench.py --full --no-cpu --no-extras --steps 5 --warmup 1 --tree-split 0 --debug $dbg $args > $OUT/$name/p$i.log 2>&1 \
       || { echo "$name pass $i failed"; tail -5 $OUT/$name/p$i.log; exit 1; }
   done
   python3 tools/pmc.py $OUT/$name > $OUT/$name.json || exit 1
