@@ -2,8 +2,9 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use this
 module, and only as the checker / the CPU baseline -- never as the product path.
-Parity status: see psoracle.c (reference unbuildable here; pinned to the reference's
-recorded C1/C2/C3 counts and its marching-cubes table; vertex bits "parity unpinned").
+Parity status: see psoracle.c (pinned to the compiled reference by tests/test_reference.py:
+the SSE build bit for bit on everything, the IEEE build bit for bit on trees without Disc /
+Ring / RicciBlend; psref.py wraps the compiled reference).
 """
 from __future__ import annotations
 
@@ -128,8 +129,8 @@ def field_value(model, x, y, z, sse_approx: bool = False) -> np.ndarray:
     return out
 
 
-def field_value_and_color(model, x, y, z):
-    L = lib()
+def field_value_and_color(model, x, y, z, sse_approx: bool = False):
+    L = lib(sse_approx)
     ref = _ref(model)
     x, y, z = (np.ascontiguousarray(a, np.float32) for a in (x, y, z))
     f = np.zeros(len(x), np.float32)

@@ -1,0 +1,236 @@
+"""The CPU oracle pinned to the reference itself, compiled (oracle/psref.py: PS::SIMDPOLY built
+in place by `make -C oracle ref` against a serial TBB stand-in).  CPU only.
+
+* 2a  the oracle's -DPSOR_SSE_APPROX build equals the reference bit for bit on every array:
+      C1, C2, C3 (slow) and 120 seeded trees over every primitive and operator, plus
+      fieldValue / fieldValueAndColor at sample quads and CountMPUNeeded;
+* 2b  the IEEE oracle (what the HIP path is held to) equals it bit for bit on trees without
+      Disc, Ring and RicciBlend, normals within 2e-3 (the one rsqrtps left, :1619);
+* 2c  on trees with those nodes the IEEE oracle deviates; how far is measured and held to
+      twice what tests/golden/reference/deviation.json records;
+* 2d  the same for PrepareBBoxes, whose FastSqrt is compiler-dependent in the reference;
+* the recorded reference outputs tests/golden/reference/*.npz against the IEEE oracle: these
+  run everywhere, the others skip where neither the library nor the reference source exists.
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import reference_util as ru
+from parity_util import assert_bits_equal
+from parsip_amd import soa, synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NORMALS_ATOL = 2e-3  # rsqrtps is specified to 1.5 * 2^-12 relative
+
+
+@pytest.fixture(scope="module")
+def ref(oracle):
+    import psref
+
+    if not psref.source_present() and not os.path.exists(os.path.join(psref.REF_DIR, "libpsref.so")):
+        pytest.skip(f"no compiled reference in oracle/_ref and no reference source at {psref.source_dir()}")
+    assert psref.available()
+    return psref
+
+
+def test_reference_builds_where_its_source_is():
+    """With the source directory present the libraries build on demand: nothing here may skip."""
+    import psref
+
+    if not psref.source_present():
+        pytest.skip(f"no reference source at {psref.source_dir()}")
+    assert psref.available() and psref.available(big=True)
+    assert psref.max_mpus() == soa.MAX_MPU_COUNT and psref.max_mpus(big=True) >= 37 ** 3
+
+
+# ---------------------------------------------------------------------------
+# 2a: the SSE build of the oracle is the reference, bit for bit
+def _probe_counts(mesh):
+    st = mesh.stats
+    return {"mpus": len(st), "passed_s1": int(np.count_nonzero(st[:, 0])), "vertices": int(st[:, 2].sum()),
+            "triangles": int(st[:, 3].sum())}
+
+
+@pytest.mark.parametrize("name", ["C1", "C2"])
+def test_sse_oracle_equals_reference_configs(ref, oracle, name):
+    model, cs, _ = synth.make_config(name)
+    r = ref.polygonize(model, cs)
+    with open(os.path.join(GOLDEN, "reference_probe.json")) as f:
+        assert _probe_counts(r) == json.load(f)[name]
+    ru.assert_oracle_mesh_equal(oracle.polygonize(model, cs, threads=8, sse_approx=True), r, name)
+
+
+@pytest.mark.slow
+def test_sse_oracle_equals_reference_c3(ref, oracle):
+    """C3's 37^3 = 50,653 MPUs through the build with MAX_MPU_COUNT raised; regenerates the
+    C3 numbers of tests/golden/reference_probe.json live."""
+    model, cs, _ = synth.make_config("C3")
+    r = ref.polygonize(model, cs, big=True)
+    with open(os.path.join(GOLDEN, "reference_probe.json")) as f:
+        g = json.load(f)["C3"]
+    got = dict(_probe_counts(r), max_vertices_per_mpu=int(r.stats[:, 2].max()),
+               max_triangles_per_mpu=int(r.stats[:, 3].max()))
+    assert got == g
+    ru.assert_oracle_mesh_equal(oracle.polygonize(model, cs, threads=os.cpu_count() or 1, sse_approx=True), r, "C3")
+
+
+def _check_quads(ref, oracle, model, cs, seed, sse):
+    x, y, z = ru.quads(model, cs, ru.N_QUADS, seed)
+    assert_bits_equal(oracle.field_value(model, x, y, z, sse_approx=sse), ref.field_value(model, x, y, z),
+                      "fieldValue at quads")
+    of, oc = oracle.field_value_and_color(model, x, y, z, sse_approx=sse)
+    rf, rc = ref.field_value_and_color(model, x, y, z)
+    assert_bits_equal(of, rf, "fieldValueAndColor field")
+    assert_bits_equal(oc, rc, "fieldValueAndColor colour")
+
+
+@pytest.mark.parametrize("seed", ru.SSE_SEEDS)
+def test_sse_oracle_equals_reference_trees(ref, oracle, seed):
+    model, cs = ru.tree_case(seed)  # the tree's prepared boxes feed both sides
+    r = ref.polygonize(model, cs)
+    ru.assert_oracle_mesh_equal(oracle.polygonize(model, cs, threads=4, sse_approx=True), r, f"seed {seed}")
+    _check_quads(ref, oracle, model, cs, seed, sse=True)
+
+
+def test_sse_tree_family(oracle):
+    """What 2a asks of its inputs: >= 120 trees, every primitive and operator type, matrices on
+    and off, non-round cell sizes, <= 4096 MPUs, at most 15 % empty meshes."""
+    import test_gpu_fuzz
+
+    assert ru.ALL_TYPES == test_gpu_fuzz.TYPES and ru.ALL_OPS == test_gpu_fuzz.OPS
+    prims, ops, mats, empty = set(), set(), set(), 0
+    for s in ru.SSE_SEEDS:
+        model, cs = ru.tree_case(s)
+        p, o = ru.node_types(model)
+        prims |= set(p)
+        ops |= set(o)
+        mats.add(bool(model.prims["idxMatrix"][0, :model.ct_prims].any()))
+        assert soa.count_mpus(cs, *model.bbox) <= 4096
+        assert 4.0 / cs != round(4.0 / cs)  # the cells do not tile the box exactly
+        empty += int(oracle.polygonize(model, cs, threads=4, keep=False).stats[:, 2].sum()) == 0
+    assert len(ru.SSE_SEEDS) >= 120
+    assert prims == set(ru.ALL_TYPES) and ops == set(ru.ALL_OPS) and mats == {False, True}
+    assert empty <= 0.15 * len(ru.SSE_SEEDS), empty
+
+
+def test_count_mpus_equals_reference(ref, oracle):
+    """CountMPUNeeded on the 200 boxes of test_oracle.test_count_mpus_lattice."""
+    rng = np.random.default_rng(0)
+    for _ in range(200):
+        lo = rng.uniform(-5, 0, 3).astype(np.float32)
+        hi = (lo + rng.uniform(0.1, 9, 3)).astype(np.float32)
+        cs = float(np.float32(rng.uniform(0.01, 0.3)))
+        n = ref.count_mpus(cs, lo, hi)
+        assert n == oracle.count_mpus(cs, lo, hi) == soa.count_mpus(cs, lo, hi)
+    assert ref.count_mpus(8 / 256, (-4, -4, -4), (4, 4, 4)) == 37 ** 3
+
+
+# ---------------------------------------------------------------------------
+# 2b: the IEEE oracle on trees free of the approximations
+@pytest.mark.parametrize("seed", ru.EXACT_SEEDS)
+def test_ieee_oracle_equals_reference_exact_trees(ref, oracle, seed):
+    model, cs = ru.exact_case(seed)
+    assert not ru.has_approx(model)
+    r = ref.polygonize(model, cs)
+    ru.assert_oracle_mesh_equal(oracle.polygonize(model, cs, threads=4), r, f"seed {seed}", normals_atol=NORMALS_ATOL)
+    _check_quads(ref, oracle, model, cs, seed, sse=False)
+
+
+def test_exact_tree_family(oracle):
+    """2b's inputs: POINT, LINE, CYLINDER, CUBE, TRIANGLE and NULL, every operator but
+    RICCIBLEND, and at least 60 trees that produce a mesh."""
+    prims, ops, meshes = set(), set(), 0
+    for s in ru.EXACT_SEEDS:
+        model, cs = ru.exact_case(s)
+        p, o = ru.node_types(model)
+        prims |= set(p)
+        ops |= set(o)
+        meshes += int(oracle.polygonize(model, cs, threads=4, keep=False).stats[:, 2].sum()) > 0
+    assert prims == set(ru.EXACT_TYPES) and ops == set(ru.EXACT_OPS)
+    assert meshes >= 60, meshes
+
+
+# ---------------------------------------------------------------------------
+# 2c / 2d: the envelope of the deliberate deviations, measured against the reference binary
+def _recorded():
+    with open(os.path.join(ru.GOLDEN_REF, "deviation.json")) as f:
+        return json.load(f)
+
+
+def test_ieee_deviation_on_approx_trees(ref, oracle):
+    """Trees with Disc, Ring or RicciBlend: the IEEE oracle is NOT the reference there.  No
+    tolerance is fixed in advance; each quantity is at most twice its recorded measurement (the
+    point sample is finite, and rsqrtps / rcpps bits differ between CPU vendors within their
+    specification).  Normals get no bound: where the topology differs by a vertex they are
+    unrelated (recorded maximum ~1.3 per component)."""
+    rec = _recorded()["approx_trees"]
+    got = ru.measure_deviation(ref, oracle)
+    print("measured", got, "recorded", rec)
+    assert got["trees"] == rec["trees"] >= 100
+    for k in ("field_max_abs", "mpu_vt_differ_share", "pos_max_abs", "pos_max_abs_same_triangles"):
+        assert got[k] <= 2 * rec[k], (k, got[k], rec[k])
+    assert np.isfinite(got["nrm_max_abs"])
+
+
+def test_prepare_bboxes_against_reference(ref, oracle):
+    """PrepareBBoxes on matrix-free trees: everything but the boxes is byte-equal; the boxes
+    differ (deviation a3: exact iso distance here, FastSqrt's compiler-dependent result
+    there), by at most twice the recorded measurement.  Box bits are not asserted."""
+    rec = _recorded()["boxes"]
+    got = ru.measure_boxes(ref, oracle)
+    print("measured", got, "recorded", rec)
+    assert got["trees"] == rec["trees"] >= 30
+    assert got["non_box_fields_differing"] == []
+    assert got["box_max_abs"] <= 2 * rec["box_max_abs"]
+    assert got["oracle_inside_reference_max"] <= 2 * rec["oracle_inside_reference_max"]
+
+
+# ---------------------------------------------------------------------------
+# recorded reference outputs: run everywhere, no reference binary needed
+def test_recorded_fixture_set():
+    """C1 and six to eight approximation-free trees; together every primitive and operator of
+    2b, all four warps, matrices on and off; sizes within what a committed fixture may take."""
+    with open(os.path.join(ru.GOLDEN_REF, "index.json")) as f:
+        idx = json.load(f)["fixtures"]
+    names = ru.fixture_names()
+    assert names[0] == "C1" and 6 <= len(names) - 1 <= 8
+    prims, ops, mats, total = set(), set(), set(), 0
+    for n in names:
+        model, cs, d, mesh = ru.load_fixture(n)
+        p, o = ru.node_types(model)
+        assert [ru.TYPE_NAMES[t] for t in p] == idx[n]["prims"] and [ru.TYPE_NAMES[t] for t in o] == idx[n]["ops"]
+        assert not ru.has_approx(model)
+        assert len(mesh.stats) == soa.count_mpus(cs, *model.bbox) <= 512 and len(mesh.pos) >= 200
+        assert len(d["quad_field"]) == 4 * 256 and len(d["point_field"]) == 256
+        size = os.path.getsize(os.path.join(ru.GOLDEN_REF, n + ".npz"))
+        assert size <= 100_000, (n, size)
+        total += size
+        prims |= set(p)
+        ops |= set(o)
+        mats.add(bool(model.prims["idxMatrix"][0, :model.ct_prims].any()))
+    assert total <= 600_000
+    assert prims == set(ru.EXACT_TYPES) and ops == set(ru.EXACT_OPS) and mats == {False, True}
+
+
+@pytest.mark.parametrize("name", ru.fixture_names())
+def test_recorded_reference_equals_ieee_oracle(oracle, name):
+    model, cs, d, mesh = ru.load_fixture(name)
+    ru.assert_oracle_mesh_equal(oracle.polygonize(model, cs, threads=4), mesh, name, normals_atol=NORMALS_ATOL)
+    q = d["quad_xyz"]
+    assert_bits_equal(oracle.field_value(model, q[:, 0], q[:, 1], q[:, 2]), d["quad_field"], "fieldValue at quads")
+    rep = np.repeat(q[::4], 4, axis=0)
+    f, c = oracle.field_value_and_color(model, rep[:, 0], rep[:, 1], rep[:, 2])
+    assert_bits_equal(f[::4], d["point_field"], "fieldValueAndColor field")
+    assert_bits_equal(c[::4], d["point_colour"], "fieldValueAndColor colour")
+
+
+@pytest.mark.parametrize("name", ru.fixture_names())
+def test_recorded_reference_is_live_reference(ref, name):
+    """The committed files are what the reference gives today (normals: this CPU's rsqrtps)."""
+    model, cs, d, mesh = ru.load_fixture(name)
+    ru.assert_oracle_mesh_equal(ref.polygonize(model, cs), mesh, name, normals_atol=NORMALS_ATOL)
+    q = d["quad_xyz"]
+    assert_bits_equal(ref.field_value(model, q[:, 0], q[:, 1], q[:, 2]), d["quad_field"], "fieldValue at quads")
