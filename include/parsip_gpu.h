@@ -239,6 +239,49 @@ int  psgpu_mesh_device(psgpu_ctx* ctx, PsMeshDevice* out);
  * ctMPUs + 1 entries as in PsMeshDevice. */
 int  psgpu_download_mesh(psgpu_ctx* ctx, float* pos, float* nrm, float* col, uint32_t* tris,
                          uint64_t* mpuOffsets);
+/* ---- watertight indexed mesh: the weld of a finished run --------------------
+ * The compact mesh concatenates per-MPU meshes, so a vertex on a face shared by two MPUs
+ * appears once per MPU (up to four times on an edge line), and for most cell sizes the copies
+ * differ in their last bits (each MPU computes the corner from its own origin).  The weld
+ * merges them by identity, not by comparing floats: input vertex gi = mpuOffsets[w] + vid
+ * sits on the global lattice edge (7 i + sx, 7 j + sy, 7 k + sz, axis), (i, j, k) the MPU
+ * w + mpuBegin in x-major order, and
+ *   - two input vertices are one welded vertex iff their edges are equal;
+ *   - welded vertices are ordered by their smallest input index and take that vertex's
+ *     position, normal and colour bit for bit;
+ *   - vertexMap[gi] is the welded id of gi; triangles keep their order and become
+ *     vertexMap[tris] (none drops: an MPU has one vertex per edge);
+ *   - seams towards MPUs outside the processed range stay open.
+ * The result depends on the run alone: welding twice gives the same bytes.  A weld leaves the
+ * run's own buffers (PsMeshDevice) and the context untouched; its buffers are allocated on
+ * the first psgpu_weld, so a context that never welds pays nothing. */
+typedef struct PsWeldInfo {
+    uint32_t ctVertices;      /* welded                                              */
+    uint32_t ctTriangles;     /* == the run's                                        */
+    uint32_t ctInputVertices; /* the run's                                           */
+    uint32_t ctSeamVertices;  /* input vertices on an MPU face                       */
+} PsWeldInfo;
+typedef struct PsWeldDevice {    /* valid until the next psgpu_weld / psgpu_destroy   */
+    const float*    pos;         /* ctVertices * 3                                    */
+    const float*    nrm;
+    const float*    col;
+    const uint32_t* tris;        /* ctTriangles * 3, welded vertex ids                */
+    const uint32_t* vertexMap;   /* ctInputVertices entries                           */
+} PsWeldDevice;
+/* Weld the context's finished run on the context's stream; blocking.  PSGPU_RET_PARAM_ERROR
+ * when there is no finished run: none yet, or a psgpu_set_model / psgpu_polygonize since the
+ * last psgpu_finish; and when the run reported an overflow MPU (its records are cut) or a
+ * lattice axis has 2^20 / 7 MPUs or more.  An empty mesh welds to an empty mesh. */
+int  psgpu_weld(psgpu_ctx* ctx, PsWeldInfo* info);
+/* The welded mesh in HBM / on the host (any pointer may be NULL): PSGPU_RET_PARAM_ERROR
+ * before a successful psgpu_weld of the current run. */
+int  psgpu_weld_device(psgpu_ctx* ctx, PsWeldDevice* out);
+int  psgpu_download_weld(psgpu_ctx* ctx, float* pos, float* nrm, float* col, uint32_t* tris,
+                         uint32_t* vertexMap);
+/* hipEvent times (ms) of the last psgpu_weld run with PSGPU_OPT_KERNEL_TIMING set: the whole
+ * weld, then its five launches; returns the count filled. */
+int  psgpu_weld_times(psgpu_ctx* ctx, float* ms, int maxPhases, const char** names);
+
 /* Per-MPU stats for every MPU in the last processed range (ctMPUs entries). */
 int  psgpu_download_stats(psgpu_ctx* ctx, PsMpuStats* stats);
 /* Scatter the last result into the reference PolyMPUs layout (vMPUs[0..ctMPUs)). */

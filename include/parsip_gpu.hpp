@@ -192,6 +192,33 @@ public:
     }
     int finish(PsMeshInfo* info) { return psgpu_finish(ctx_.get(), info); }
     int mesh(PsMeshDevice* out) { return psgpu_mesh_device(ctx_.get(), out); }
+    /* The finished run's mesh welded by lattice-edge identity (psgpu_weld: one vertex per
+     * lattice edge, watertight across MPU seams), its counts and host copies. */
+    struct Welded {
+        PsWeldInfo info{};
+        std::vector<float> pos, nrm, col;  /* info.ctVertices * 3 each */
+        std::vector<uint32_t> tris;        /* info.ctTriangles * 3, welded ids */
+        std::vector<uint32_t> vertexMap;   /* info.ctInputVertices */
+    };
+    /* After finish(); PSGPU_RET_PARAM_ERROR without a finished run (out is left empty). */
+    int weld(Welded* out) {
+        if (!ctx_.ok()) return ctx_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Welded();
+        PsWeldInfo info;
+        const int rc = psgpu_weld(ctx_.get(), &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->info = info;
+        out->pos.resize(size_t(info.ctVertices) * 3);
+        out->nrm.resize(size_t(info.ctVertices) * 3);
+        out->col.resize(size_t(info.ctVertices) * 3);
+        out->tris.resize(size_t(info.ctTriangles) * 3);
+        out->vertexMap.resize(info.ctInputVertices);
+        return psgpu_download_weld(ctx_.get(), out->pos.data(), out->nrm.data(), out->col.data(), out->tris.data(),
+                                   out->vertexMap.data());
+    }
+    /* The same weld left in HBM (valid until the next weld). */
+    int weldDevice(PsWeldDevice* out) { return psgpu_weld_device(ctx_.get(), out); }
     Context& context() { return ctx_; }
 
 private:

@@ -1154,6 +1154,7 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->tier2Fut = JitFuture();
     c->jit.reset();
     c->jit1.reset();
+    weld_free(c);
     void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->pqOct, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
                     c->pos, c->nrm, c->col, c->tris, c->ctr, c->totals, c->stamps, c->spans, c->mpuTicks};
     for (void* b : bufs)
@@ -1194,6 +1195,7 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
         c->vShardCap = (uint32_t)std::max<int64_t>(16, value / kShards);
         c->tShardCap = 2 * c->vShardCap;
         c->haveResult = false;
+        ++c->runSeq;
     }
     else if (option == PSGPU_OPT_VERTEX_BLOCKS_PER_CU && value >= 1 && value <= 32) c->vertexBlocksPerCU = (int)value;
     else if (option == PSGPU_OPT_FINISH_BLOCKS_PER_CU && value >= 1 && value <= 32) c->finishBlocksPerCU = (int)value;
@@ -1280,6 +1282,7 @@ int psgpu_set_model(psgpu_ctx* c, const PsSoaBlobPrims* prims, const PsSoaPrimMa
         PSGPU_CHECK(hipStreamSynchronize(c->stream));
     }
     c->haveModel = true;
+    ++c->runSeq;  // a weld belongs to a finished run of the current model
     if (!same || (!c->jit && !c->jitPending)) jit_start(c);
     return PSGPU_RET_SUCCESS;
 }
@@ -1340,6 +1343,7 @@ int psgpu_polygonize(psgpu_ctx* c, float cellsize, uint32_t mpuBegin, uint32_t m
     c->runStream = s;
     set_pending(c, true);
     c->haveResult = false;
+    ++c->runSeq;
     return PSGPU_RET_SUCCESS;
 }
 
@@ -1442,6 +1446,7 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
                         : (c->runSplit ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->runSurface ? PSGPU_LAUNCH_SURFACE : 0u) |
                               (c->runFront ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u);
         c->haveResult = true;
+        c->finishedSeq = c->runSeq;
         if (c->countThreads) thread_results_add(c->serial, I.ctMPUs, I.ctSurfaceMPUs);
     }
     if (!c->haveResult) return PSGPU_RET_PARAM_ERROR;

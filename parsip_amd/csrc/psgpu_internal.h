@@ -23,6 +23,26 @@ namespace psgpu {
 constexpr int kExportPieces = 16;  // at most, in the blocking export (psgpu_host.cpp export_stage)
 constexpr size_t kExportPieceBytes = 1u << 20;  // its target piece size
 
+// The device weld of a finished run (psgpu_weld.hip): its own buffers, allocated on the first
+// psgpu_weld of the context, grown on demand, freed by psgpu_destroy (weld_free).
+constexpr int kWeldPhases = 6;  // psgpu_weld_times: the whole weld, then its five launches
+struct WeldState {
+    unsigned char* table = nullptr;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
+    uint32_t* rep = nullptr;         // per input vertex: its representative (the smallest index on its edge)
+    uint32_t* kid = nullptr;         // per kept input vertex: its welded id
+    uint32_t* map = nullptr;         // vertexMap
+    uint64_t* blockCnt = nullptr;    // per block of vertices: kept | seam << 32, scanned
+    float* pos = nullptr;            // the welded mesh
+    float* nrm = nullptr;
+    float* col = nullptr;
+    uint32_t* tris = nullptr;
+    size_t capTable = 0, capV = 0, capBlocks = 0, capV3 = 0, capT3 = 0;
+    uint64_t doneSeq = ~0ull;        // psgpu_ctx::runSeq of the run the buffers hold the weld of
+    PsWeldInfo info{};
+    hipEvent_t ev[kWeldPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: around the launches
+    float lastMs[kWeldPhases] = {};
+};
+
 }  // namespace psgpu
 
 struct psgpu_ctx {
@@ -165,6 +185,10 @@ struct psgpu_ctx {
     // high-water marks of finished runs: the next run's buffers are sized from them
     // (an animation whose mesh grows frame to frame does not pay a synchronous re-run)
     uint32_t seenV = 0, seenT = 0, seenShardV = 0, seenShardT = 0;
+    // psgpu_weld: runSeq counts whatever supersedes a result (set_model, polygonize, a
+    // capacity restart), finishedSeq is its value when psgpu_finish last collected a run
+    uint64_t runSeq = 0, finishedSeq = ~0ull;
+    psgpu::WeldState weld;
 };
 
 
@@ -173,6 +197,8 @@ namespace psgpu {
 int hip_fail(hipError_t e, const char* what);
 // Make the context's device current on the calling thread.
 int set_device(psgpu_ctx* c);
+// Free the weld's buffers and events (psgpu_weld.hip); the context's device is current.
+void weld_free(psgpu_ctx* c);
 // The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.

@@ -51,6 +51,15 @@ class PsMeshDevice(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "nrm", "col", "tris", "mpuOffsets")]
 
 
+class PsWeldInfo(ctypes.Structure):
+    _fields_ = [("ctVertices", ctypes.c_uint32), ("ctTriangles", ctypes.c_uint32),
+                ("ctInputVertices", ctypes.c_uint32), ("ctSeamVertices", ctypes.c_uint32)]
+
+
+class PsWeldDevice(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "nrm", "col", "tris", "vertexMap")]
+
+
 EXPORTED_SYMBOLS = [
     "psgpu_count_mpus", "psgpu_mpu_dims", "psgpu_prepare_bboxes", "psgpu_translate_blobtree_type",
     "psgpu_tritable", "psgpu_version", "psgpu_create", "psgpu_destroy", "psgpu_device_count",
@@ -66,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_result", "psgpu_download_stamps", "psgpu_comm_exchange_group", "psgpu_download_spans",
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
+    "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -171,6 +181,10 @@ def load(build_if_missing: bool = True):
         "psgpu_comm_exchange_group": ([vp, vp], i32),
         "psgpu_comm_result": ([vp, ctypes.POINTER(PsMeshInfo), vp], i32),
         "psgpu_comm_reexchanged": ([vp], i32),
+        "psgpu_weld": ([vp, ctypes.POINTER(PsWeldInfo)], i32),
+        "psgpu_weld_device": ([vp, ctypes.POINTER(PsWeldDevice)], i32),
+        "psgpu_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
+        "psgpu_weld_times": ([vp, vp, i32, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -287,6 +301,19 @@ class Mesh:
         per = np.repeat(self.vertex_offsets[:-1].astype(np.int64),
                         np.diff(self.triangle_offsets).astype(np.int64))
         return (self.tris.astype(np.int64) - per[:, None]).astype(np.uint16)
+
+
+@dataclass
+class WeldedMesh:
+    """The finished run's mesh welded by lattice-edge identity (psgpu_weld): one vertex per
+    lattice edge, in first-occurrence order, with the first occurrence's attributes."""
+
+    pos: np.ndarray         # (Vw,3) f32
+    nrm: np.ndarray         # (Vw,3) f32
+    col: np.ndarray         # (Vw,3) f32
+    tris: np.ndarray        # (T,3) u32 welded vertex ids, the run's triangle order
+    vertex_map: np.ndarray  # (V,) u32: welded id of every input vertex
+    info: PsWeldInfo
 
 
 class Polygonizer:
@@ -426,6 +453,39 @@ class Polygonizer:
         d = PsMeshDevice()
         _check(self._L.psgpu_mesh_device(self._ctx, ctypes.byref(d)), "psgpu_mesh_device")
         return d
+
+    def weld_info(self) -> PsWeldInfo:
+        """psgpu_weld on the finished run (``finish()`` or ``run()`` first): the welded mesh
+        stays in HBM (``weld_device()``); returns its counts."""
+        info = PsWeldInfo()
+        _check(self._L.psgpu_weld(self._ctx, ctypes.byref(info)), "psgpu_weld")
+        return info
+
+    def weld(self) -> WeldedMesh:
+        """Weld the finished run on the device and download the watertight indexed mesh."""
+        info = self.weld_info()
+        V, T, Vin = info.ctVertices, info.ctTriangles, info.ctInputVertices
+        pos = np.zeros((V, 3), np.float32)
+        nrm = np.zeros((V, 3), np.float32)
+        col = np.zeros((V, 3), np.float32)
+        tris = np.zeros((T, 3), np.uint32)
+        vmap = np.zeros(Vin, np.uint32)
+        _check(self._L.psgpu_download_weld(self._ctx, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data,
+                                           tris.ctypes.data, vmap.ctypes.data), "psgpu_download_weld")
+        return WeldedMesh(pos, nrm, col, tris, vmap, info)
+
+    def weld_device(self) -> PsWeldDevice:
+        """Device pointers of the last weld of the current run (valid until the next weld)."""
+        d = PsWeldDevice()
+        _check(self._L.psgpu_weld_device(self._ctx, ctypes.byref(d)), "psgpu_weld_device")
+        return d
+
+    def weld_times(self) -> dict:
+        """hipEvent times (ms) of the last weld (OPT_KERNEL_TIMING): the whole weld and its launches."""
+        ms = (ctypes.c_float * 8)()
+        names = (ctypes.c_char_p * 8)()
+        n = self._L.psgpu_weld_times(self._ctx, ms, 8, names)
+        return {names[i].decode(): ms[i] for i in range(n)}
 
     def mpu_costs(self) -> np.ndarray:
         """Per-MPU lane-evaluations of the last run (balances ranges across devices)."""

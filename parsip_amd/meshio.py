@@ -11,6 +11,9 @@ vertex_indices", written in stream order).  Here:
   `gpu.Polygonizer.export_polympus`) into one compact mesh, MPU by MPU, as draw() walks it;
 * `weld` merges the duplicate vertices MPUs emit on shared faces (exact position bits;
   the reference keeps them, since every MPU is drawn on its own);
+* `weld_lattice` merges them by the lattice edge each vertex sits on instead (exact for every
+  cell size: neighbouring MPUs round a shared corner differently, DESIGN.md §6 "Weld"); the
+  device form is `gpu.Polygonizer.weld`;
 * `write_off`, `write_ply` follow CMeshVV::save's text layouts; `write_obj` adds the
   common OBJ form with normals (v / vn / f a//a b//b c//c).
 """
@@ -19,6 +22,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 
 import numpy as np
+
+from . import soa
 
 
 @dataclass
@@ -79,6 +84,100 @@ def weld(mesh: TriMesh) -> TriMesh:
     ok = (tris[:, 0] != tris[:, 1]) & (tris[:, 1] != tris[:, 2]) & (tris[:, 0] != tris[:, 2])
     return TriMesh(mesh.pos[keep], tris[ok], None if mesh.nrm is None else mesh.nrm[keep],
                    None if mesh.col is None else mesh.col[keep])
+
+
+def lattice_edges(mesh, vertex_offsets, cellsize: float, lo, hi, mpu_begin: int = 0) -> np.ndarray:
+    """The global lattice edge (gx, gy, gz, axis) of every vertex of a concatenation of per-MPU
+    meshes (arguments as `weld_lattice`), (V, 4) int64, recovered from the positions: a vertex
+    of MPU (i, j, k) on the edge from corner (sx, sy, sz) along `axis` has
+    g = (7i + sx, 7j + sy, 7k + sz).  Its two off-axis coordinates equal
+    ``origin + cellsize * float(s)`` of its MPU bit for bit for some s in 0..7, the third lies
+    in cell [s, s + 1) of the axis.  ValueError on a vertex with fewer than two such
+    coordinates, and on one with three (a root exactly on a lattice corner: its axis cannot
+    be told from positions alone).  A vertex is on an MPU face iff an off-axis g is a multiple
+    of 7."""
+    pos = np.ascontiguousarray(mesh.pos, np.float32).reshape(-1, 3)
+    voff = np.asarray(vertex_offsets, np.int64)
+    n, V = len(voff) - 1, len(pos)
+    if voff[-1] != V:
+        raise ValueError(f"vertex_offsets end at {int(voff[-1])}, the mesh has {V} vertices")
+    if V == 0:
+        return np.zeros((0, 4), np.int64)
+    dims = soa.mpu_dims(cellsize, lo, hi)
+    w = np.repeat(np.arange(n, dtype=np.int64), np.diff(voff))
+    org = soa.mpu_origins(cellsize, lo, hi, mpu_begin, mpu_begin + n)[w]
+    m = w + mpu_begin
+    ijk = (m // (dims[2] * dims[1]), (m // dims[2]) % dims[1], m % dims[2])
+    cs = np.float32(cellsize)
+    steps = cs * np.arange(8, dtype=np.float32)            # cs * (float)s, one rounding
+    exact = np.zeros((V, 3), bool)
+    s = np.zeros((V, 3), np.int64)
+    cell = np.zeros((V, 3), np.int64)
+    inside = np.zeros((V, 3), bool)
+    for a in range(3):
+        corner = org[:, a, None] + steps[None, :]          # (V, 8) f32: origin + cs * s
+        hit = corner.view(np.uint32) == pos[:, a].view(np.uint32)[:, None]
+        exact[:, a] = hit.any(axis=1)
+        s[:, a] = hit.argmax(axis=1)
+        cell[:, a] = np.minimum((corner[:, 1:] <= pos[:, a, None]).sum(axis=1), 6)
+        inside[:, a] = (pos[:, a] >= corner[:, 0]) & (pos[:, a] <= corner[:, 7])
+    ct = exact.sum(axis=1)
+    if (ct < 2).any():
+        v = int(np.flatnonzero(ct < 2)[0])
+        raise ValueError(f"vertex {v} {pos[v]} is not on a lattice edge of its MPU")
+    if (ct > 2).any():
+        v = int(np.flatnonzero(ct > 2)[0])
+        raise ValueError(f"{int((ct > 2).sum())} vertices are exactly on a lattice corner (first: vertex {v} "
+                         f"{pos[v]}): their edges are ambiguous")
+    axis = (~exact).argmax(axis=1)
+    rows = np.arange(V)
+    if not inside[rows, axis].all():
+        v = int(np.flatnonzero(~inside[rows, axis])[0])
+        raise ValueError(f"vertex {v} {pos[v]} is outside its MPU")
+    s[rows, axis] = cell[rows, axis]
+    return np.stack([7 * ijk[0] + s[:, 0], 7 * ijk[1] + s[:, 1], 7 * ijk[2] + s[:, 2], axis], axis=1)
+
+
+def weld_lattice(mesh, vertex_offsets, cellsize: float, lo, hi, mpu_begin: int = 0):
+    """Merge the vertices MPUs emit on shared faces by lattice-edge identity; returns
+    ``(TriMesh, vertex_map)``.
+
+    ``mesh`` is the concatenation of per-MPU meshes of MPUs ``[mpu_begin, mpu_begin + n)`` of the
+    lattice of ``cellsize`` over the box ``lo``..``hi`` (a ``gpu.Mesh`` download, or a TriMesh
+    with global ids), ``vertex_offsets`` its ``n + 1`` per-MPU vertex offsets.  Vertices on the
+    same lattice edge (`lattice_edges`, which raises ValueError on a vertex whose edge the
+    positions do not determine) are one welded vertex, welded vertices are ordered by their
+    first occurrence and take its position, normal and colour, ``vertex_map[v]`` is the welded
+    id of input vertex v and the triangles are ``vertex_map[mesh.tris]`` (none drops: an MPU has
+    one vertex per edge).  Seams towards MPUs outside the range stay open.  The device form is
+    ``gpu.Polygonizer.weld`` (same bytes)."""
+    pos = np.ascontiguousarray(mesh.pos, np.float32).reshape(-1, 3)
+    tris_in = np.asarray(mesh.tris).astype(np.int64)
+    g = lattice_edges(mesh, vertex_offsets, cellsize, lo, hi, mpu_begin)
+    if len(pos) == 0:
+        return TriMesh(pos, tris_in, mesh.nrm, mesh.col), np.zeros(0, np.int64)
+    if max(soa.mpu_dims(cellsize, lo, hi)) * 7 >= 1 << 20:  # the device's limit too (psgpu_weld)
+        raise ValueError("lattice too large for the edge key")
+    key = (((g[:, 0] << 20 | g[:, 1]) << 20 | g[:, 2]) << 2) | g[:, 3]
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
+    order = np.argsort(first)
+    remap = np.empty_like(order)
+    remap[order] = np.arange(len(order))
+    vertex_map = remap[inverse.reshape(-1)]
+    keep = first[order]
+    return (TriMesh(pos[keep], vertex_map[tris_in], None if mesh.nrm is None else np.asarray(mesh.nrm)[keep],
+                    None if mesh.col is None else np.asarray(mesh.col)[keep]), vertex_map)
+
+
+def open_edge_count(tris) -> int:
+    """Undirected edges used by exactly one triangle (0 on a closed surface)."""
+    t = np.asarray(tris).astype(np.int64).reshape(-1, 3)
+    if len(t) == 0:
+        return 0
+    e = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]])
+    e.sort(axis=1)
+    _, counts = np.unique(e[:, 0] << 32 | e[:, 1], return_counts=True)
+    return int((counts == 1).sum())
 
 
 def _fmt(a) -> str:
