@@ -310,6 +310,11 @@ int  psgpu_download_process_stats(psgpu_ctx* ctx, PsMpuProcessStats* out);
  * XCC_ID << 16.  Unlaunched waves read zero; then cap x 8 words of k_mpu phase stamps
  * (PSGPU_OPT_DEBUG bit 4096; profiling only).  Pass out = NULL to query *cap. */
 int  psgpu_download_stamps(psgpu_ctx* ctx, uint64_t* out, uint32_t* cap);
+/* Debug export of the finished run's vertex record queue (tests, tools/batch_live.py): the 64
+ * shard counts into counts[0..64) and, with recs != NULL, every record as the pair (MPU slot in
+ * the range, MPU-local vertex id), shard after shard in queue order: 2 x sum(counts) words.
+ * capacity is in records; PSGPU_RET_PARAM_ERROR if it is short (counts is still written). */
+int  psgpu_vertex_queue(psgpu_ctx* ctx, uint32_t* counts, uint32_t* recs, uint32_t capacity);
 /* PrintThreadResults (PS_Polygonizer.h:393, body .cpp:414-428, counters .cpp:443-469).
  * The reference keeps one (processed, crossed) MPU count pair per TBB worker that ran an
  * MPU, accumulated over every Polygonize of the process.  Here the worker is a device

@@ -1219,6 +1219,11 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     const CubeTablesDev* tab = p.tables;  // global: L1 / L2 resident (an LDS copy per block measured slower, r05)
     bool live;
     uint32_t slotq = 0;
+    // PSGPU_BLOCK_RESERVE 1: the block's MPUs exchange their V (0 without surface) and arrive here
+    // after S3 pass 1; the last one reserves the block's vertex records with one atomic (zeroed
+    // before the prologue's barrier, which every wave of the block reaches)
+    __shared__ uint32_t sResV[MPB], sResArrive, sResBase;
+    if (PSGPU_BLOCK_RESERVE == 1 && threadIdx.x == 0) sResArrive = 0u;
     if constexpr (FRONT) {
         const uint32_t q = blk & 7u, e = (blk >> 3) * (uint32_t)MPB + (uint32_t)slot;
         d = (e << 3) | q;  // spreads the MPU's vertex records over the shards
@@ -1311,7 +1316,8 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
         mpu_origin(p, m, o);
     }
     phase_stamp(p, 1);
-    if (WPM == 1 && !live) return;
+    // (block reservation: a wave without work still joins the block's barrier after pass 1)
+    if (PSGPU_BLOCK_RESERVE != 1 && WPM == 1 && !live) return;
     unsigned char* base = smem + slot * kLdsMpu;
     uint16_t* edgeVid = reinterpret_cast<uint16_t*>(base + kLdsEdge);
     uint8_t* cellCfg = base + kLdsCfg;
@@ -1408,7 +1414,7 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     }
     const bool work = live && inside != 0 && inside != 512 && !(p.debug & 1u);
     if (live && !work && part == 0 && lane == 0) p.counts[w] = 0ull;  // no vertices, no triangles
-    if (WPM == 1 && !work) return;
+    if (PSGPU_BLOCK_RESERVE != 1 && WPM == 1 && !work) return;
 
     // S3 pass 1 (:647-691): config per cell (bit c = x*4 + y*2 + z, inside = f >= 0.5),
     // owned sign-changing edges (new vertices) and triangles; wave prefix sums give
@@ -1454,7 +1460,8 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
         if (part == 0) {
             const uint32_t shard = d & (kShards - 1);
             if (lane == 0) {
-                qvAtomic = atomicAdd(&p.ctr->shard[shard].v, V);
+                if (PSGPU_BLOCK_RESERVE != 1)
+                    qvAtomic = atomicAdd(&p.ctr->shard[PSGPU_BLOCK_RESERVE ? blk & (kShards - 1) : shard].v, V);
                 qtAtomic = atomicAdd(&p.ctr->shard[w & (kShards - 1)].t, T);  // TriRec: shard = w & 63
                 if (WPM > 1) {
                     sQ[0] = qvAtomic;
@@ -1476,10 +1483,30 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
                 (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | ((uint64_t)V << 16) | ((uint64_t)T << 32);
     }
 #endif
-    mpu_sync<WPM>();
     const bool recs = work && !(p.debug & 2u);  // ablation bit 1: pass 1 only
+    if (PSGPU_BLOCK_RESERVE == 1) {
+        // the block's rendezvous: every MPU leaves its V in slot order and counts itself in; the
+        // last to arrive has all of them and reserves their sum in shard blk & 63.  Its wait for
+        // the atomic is the block's: the base is published at the barrier (making each wave's
+        // first batch of records before the barrier, to hide that wait, measured the same:
+        // profiles/r07_block_reserve_ab.txt)
+        if (part == 0 && lane == 0) {
+            sResV[slot] = V;
+            if (__hip_atomic_fetch_add(&sResArrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) ==
+                (uint32_t)MPB - 1u) {
+                uint32_t sum = 0;
+#pragma unroll
+                for (int k = 0; k < MPB; ++k) sum += sResV[k];
+                sResBase = sum ? atomicAdd(&p.ctr->shard[blk & (kShards - 1)].v, sum) : 0u;
+            }
+        }
+        __syncthreads();
+        if (WPM == 1 && !work) return;
+    } else {
+        mpu_sync<WPM>();
+    }
     const uint32_t shard = d & (kShards - 1);
-    VertexKey* vk = p.vk + (size_t)shard * p.vShardCap;
+    VertexKey* vk = p.vk + (size_t)(PSGPU_BLOCK_RESERVE ? blk & (kShards - 1) : shard) * p.vShardCap;
     TriRec* tq = p.tq + (size_t)(w & (kShards - 1)) * p.tShardCap;
 
     // pass 2 (:703-762), one lane per new vertex r (batches of 64 dealt to the MPU's waves
@@ -1488,6 +1515,12 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     // Records are written coalesced.
     if (recs) {
         uint32_t qv = WPM > 1 ? sQ[0] : 0u;
+        if (PSGPU_BLOCK_RESERVE == 1) {  // the block's base + the V of its earlier slots
+            qv = sResBase;
+#pragma unroll
+            for (int k = 0; k < MPB - 1; ++k)
+                if (k < slot) qv += sResV[k];
+        }
         for (uint32_t b0 = (uint32_t)part * 64u; b0 < V; b0 += 64u * WPM) {
             const uint32_t r = b0 + (uint32_t)lane;
             if (r < V) {
@@ -1510,8 +1543,9 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
                 const int sx = i + ((c1 >> 2) & 1), sy = j + ((c1 >> 1) & 1), sz = k + (c1 & 1);
                 edgeVid[((sx * 8 + sy) * 8 + sz) * 3 + ax] = (uint16_t)r;
                 const uint32_t key = (uint32_t)sx | ((uint32_t)sy << 3) | ((uint32_t)sz << 6) | ((uint32_t)ax << 9);
-                if (WPM == 1) {  // lane 0's atomic result, read only once the record is made (the
-                                 // empty asm ties the read, and the wait for the atomic, to the key)
+                if (WPM == 1 && PSGPU_BLOCK_RESERVE != 1) {  // lane 0's atomic result, read only once the record
+                                                             // is made (the empty asm ties the read, and the
+                                                             // wait for the atomic, to the key)
                     if (PSGPU_DEFER_ATOMICS) asm volatile("" : "+v"(qvAtomic) : "v"(key));
                     qv = lane_value(qvAtomic, 0);
                 }

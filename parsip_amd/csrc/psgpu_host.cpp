@@ -917,7 +917,9 @@ void reset_run_state(psgpu_ctx* c) {
 // ===========================================================================
 extern "C" {
 
-const char* psgpu_version(void) { return "parsip_amd 0.1 (gfx950)"; }
+#define PSGPU_STR2(x) #x
+#define PSGPU_STR(x) PSGPU_STR2(x)
+const char* psgpu_version(void) { return "parsip_amd 0.1 (gfx950, block reserve " PSGPU_STR(PSGPU_BLOCK_RESERVE) ")"; }
 
 void psgpu_tritable(int32_t out[256 * 16]) {
     const CubeTables& T = cube_tables();
@@ -1461,6 +1463,34 @@ int psgpu_download_stamps(psgpu_ctx* c, uint64_t* out, uint32_t* capOut) {
     if (!c->stamps || !out) return c->stamps ? PSGPU_RET_SUCCESS : PSGPU_RET_PARAM_ERROR;
     PSGPU_CHECK(hipMemcpy(out, c->stamps, (size_t)kNumStampKernels * c->stampCap * 24 + (size_t)c->stampCap * 64,
                           hipMemcpyDeviceToHost));
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_vertex_queue(psgpu_ctx* c, uint32_t* counts, uint32_t* recs, uint32_t capacity) {
+    if (!c || !counts) return PSGPU_RET_PARAM_ERROR;
+    int rc = psgpu_finish(c, nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    uint64_t total = 0;
+    for (int k = 0; k < kShards; ++k) {
+        counts[k] = c->mpuCount ? c->hostCtr->shard[k].v : 0u;
+        if (counts[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;  // finish re-runs until they fit
+        total += counts[k];
+    }
+    if (!recs) return PSGPU_RET_SUCCESS;
+    if (total > capacity) return PSGPU_RET_PARAM_ERROR;
+    rc = set_device(c);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    std::vector<VertexKey> shard;
+    for (int k = 0; k < kShards; ++k) {
+        if (counts[k] == 0) continue;
+        shard.resize(counts[k]);
+        PSGPU_CHECK(hipMemcpy(shard.data(), c->vk + (size_t)k * c->vShardCap, (size_t)counts[k] * sizeof(VertexKey),
+                              hipMemcpyDeviceToHost));
+        for (const VertexKey& K : shard) {
+            *recs++ = K.w;
+            *recs++ = K.vidKey & 0xffffu;
+        }
+    }
     return PSGPU_RET_SUCCESS;
 }
 

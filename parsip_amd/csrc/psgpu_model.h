@@ -198,6 +198,14 @@ struct DevCounters {
                            // Host and device must agree (build.py and the JIT pass the same value).
                            // C3 ms/step on one box: W=1 0.0624, W=2 0.0669, W=4 0.0722.
 #endif
+#ifndef PSGPU_BLOCK_RESERVE
+#define PSGPU_BLOCK_RESERVE 1  // k_mpu's vertex-queue reservations: 0 one per MPU into shard d & 63;
+                               // 1 one per block into shard blk & 63, the block's MPUs back to back
+                               // (the 64-record batches of k_vertex / k_finish then straddle MPUs of
+                               // one S1 brick, whose live primitive sets overlap: DESIGN.md §4);
+                               // 2 one per MPU, all of a block's into shard blk & 63.  The JIT passes
+                               // the library's value on (build.py: PSGPU_BLOCK_RESERVE=<n> for A/B).
+#endif
 constexpr int kMpuWaves = PSGPU_MPU_WAVES;
 constexpr int kMpusPerBlock = 4 / kMpuWaves;  // k_mpu blocks are 4 waves
 constexpr int kNumStampKernels = 4;  // k_precheck, k_mpu, k_vertex, k_finish

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
+    "psgpu_vertex_queue",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -185,6 +186,7 @@ def load(build_if_missing: bool = True):
         "psgpu_weld_device": ([vp, ctypes.POINTER(PsWeldDevice)], i32),
         "psgpu_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
         "psgpu_weld_times": ([vp, vp, i32, vp], i32),
+        "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -406,6 +408,18 @@ class Polygonizer:
         st = np.zeros(info.ctMPUs, soa.MPU_STATS_DTYPE)
         _check(self._L.psgpu_download_stats(self._ctx, st.ctypes.data), "psgpu_download_stats")
         return st
+
+    def vertex_queue(self) -> tuple[np.ndarray, list[np.ndarray]]:
+        """Debug export of the finished run's vertex record queue: the 64 shard counts and, per
+        shard, an (n, 2) array of the records' (MPU slot in the range, MPU-local vertex id) in
+        queue order."""
+        info = self.finish()
+        counts = np.zeros(64, np.uint32)
+        recs = np.zeros((max(info.ctVertices, 1), 2), np.uint32)
+        _check(self._L.psgpu_vertex_queue(self._ctx, counts.ctypes.data, recs.ctypes.data, len(recs)),
+               "psgpu_vertex_queue")
+        ends = np.cumsum(counts.astype(np.int64))
+        return counts, [recs[e - n:e] for e, n in zip(ends, counts.astype(np.int64))]
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info = self.finish()

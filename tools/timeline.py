@@ -212,6 +212,7 @@ def finish_phases(config="C3", share=1):
     model, cs, N = synth.make_config(config)
     p = gpu.Polygonizer(0)
     p.set_option(gpu.OPT_FINISH_QUAD, 0)
+    p.set_option(gpu.OPT_FUSED_SURFACE, 0)  # k_vertex + k_finish: a lone run otherwise takes k_surface
     p.set_model(model)
     lo, hi = _share_range(p, cs, share)
     for _ in range(3):
