@@ -35,22 +35,6 @@ __device__ __forceinline__ Instr load_instr(ModelPtr M, int pc) {
     return I;
 }
 
-// +0.0f made by an instruction of the block it is written in: the culled branch of the
-// generated walk (`else f = 0`) keeps its zeros instead of the compiler turning them into
-// constants of a phi, which it materialises before the branch, on every path
-// (PSGPU_ZERO_ASM 0: plain constants, experiments).
-#ifndef PSGPU_ZERO_ASM
-#define PSGPU_ZERO_ASM 0  // 1: isolated k_precheck / k_vertex 1-1.5 us slower, 4 engines 2 % slower (r04 A/B)
-#endif
-__device__ __forceinline__ float zero_f() {
-#if PSGPU_ZERO_ASM
-    float z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-#else
-    return 0.0f;
-#endif
-}
 __device__ __forceinline__ float max_ref(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float min_ref(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float m01(bool c) { return c ? 1.0f : 0.0f; }
@@ -67,24 +51,9 @@ __device__ __forceinline__ bool quad_any(bool v) {
     return x != 0;
 }
 
-// GROUP 5 is GROUP 4 for the S2 cache (k_mpu): the 4 lanes of a group are 4 z-consecutive
-// corners of one x-slice and one y row, and every point of a lane has the lane's y and z.
-// The generated walk uses that to test a pruned op's box once per op for y and z (the
-// group's z union by one quad OR) and per point for x alone: group_any(X | Y | Z) =
-// X | Y | group_any(Z) when X and Y are the same in the 4 lanes -- the same decisions.
-#ifndef PSGPU_S2_GROUP
-#define PSGPU_S2_GROUP 4  // 5: the per-op y/z test -- isolated k_mpu 32.3 vs 35.1 us, but four engines
-                          // in flight 0.0611-0.0624 vs 0.0555-0.0560 ms/step (r04 A/B,
-                          // profiles/r04_kernel_variants_ab.txt): kept as an experiment
-#endif
-#ifndef PSGPU_S2_OCT
-#define PSGPU_S2_OCT 0  // S2 by octant passes (k_precheck's per-octant proofs): 0 off, 1 when <= 4
-                        // octants are unproven, 2 always (two passes when 5-8 are unproven)
-#endif
-constexpr int kS2Group = PSGPU_S2_GROUP;
 template <int GROUP>
 __device__ __forceinline__ bool group_any(bool v) {
-    if (GROUP == 4 || GROUP == 5) return quad_any(v);
+    if (GROUP == 4) return quad_any(v);
     return v;
 }
 
@@ -151,20 +120,8 @@ __device__ __forceinline__ uint32_t lane_value(uint32_t v, int lane) {
 // A value the wave holds in every lane, as a scalar (SGPR): branches on it are scalar, and
 // the compiler sees the uniformity its divergence analysis cannot prove (e.g. anything
 // derived from threadIdx.x >> 6).
-#ifndef PSGPU_DEFER_ATOMICS
-#define PSGPU_DEFER_ATOMICS 1  // 0: wait for the queue reservations' atomics where they return (A/B)
-#endif
-#ifndef PSGPU_UNIFORM_CM
-#define PSGPU_UNIFORM_CM 1  // 0: k_mpu's culling mask in VGPRs (experiments)
-#endif
-#ifndef PSGPU_UNIFORM_WAVE
-#define PSGPU_UNIFORM_WAVE 0  // 1: the wave index through readfirstlane -- 2 % slower with four
-                              // engines (r04 A/B); kept as an experiment
-#endif
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int wave_index() {
-    return PSGPU_UNIFORM_WAVE ? (int)uniform(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
-}
+__device__ __forceinline__ int wave_index() { return (int)(threadIdx.x >> 6); }
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return (uint64_t)uniform((uint32_t)v) | ((uint64_t)uniform((uint32_t)(v >> 32)) << 32);
 }
@@ -914,7 +871,7 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     // the 4x4x4 corners [4X, 4X+3] x [4Y, 4Y+3] x [4Z, 4Z+3] of its S2 cache (its z range
     // is exactly one S2 quad); the wave's culling box covers every MPU of the brick.
     uint32_t proven8 = 0;
-    uint64_t octOut = 0ull, octIn = 0ull;  // per lane (MPU g, octant c): proven all outside / all inside
+    uint64_t bOut = 0ull, bIn = 0ull;  // per lane (MPU g, octant c): proven all outside / all inside
     if ((p.debug & 1024u) && flags8 != 0u) __builtin_amdgcn_s_setprio(2);  // experiment: heavy waves first
     if constexpr (SPLIT == 2) {
         __shared__ float sLo[4][64], sHi[4][64];
@@ -947,9 +904,8 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
             const int r = slot * 2, l = slot * 2 + 1;
             ok = sOk[r][lane] != 0u && sOk[l][lane] != 0u;
             ev.bound_combine(sLo[r][lane], sHi[r][lane], sLo[l][lane], sHi[l][lane], cm, &lo, &hi);
-            const uint64_t bOut = ballot(ok && hi < 0.5f), bIn = ballot(ok && lo >= 0.5f);
-            octOut = bOut;
-            octIn = bIn;
+            bOut = ballot(ok && hi < 0.5f);
+            bIn = ballot(ok && lo >= 0.5f);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const bool all = ((bOut >> (8 * q)) & 0xffull) == 0xffull || ((bIn >> (8 * q)) & 0xffull) == 0xffull;
@@ -973,9 +929,8 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
         float lo = 0.0f, hi = 0.0f;
         bool ok = true;
         ev.bound(B, cm, &lo, &hi, &ok);
-        const uint64_t bOut = ballot(ok && hi < 0.5f), bIn = ballot(ok && lo >= 0.5f);
-        octOut = bOut;
-        octIn = bIn;
+        bOut = ballot(ok && hi < 0.5f);
+        bIn = ballot(ok && lo >= 0.5f);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const bool all = ((bOut >> (8 * q)) & 0xffull) == 0xffull || ((bIn >> (8 * q)) & 0xffull) == 0xffull;
@@ -1032,7 +987,7 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
             }
         }
     }
-    if (PSGPU_DEFER_ATOMICS) asm volatile("" : "+v"(baseAtomic) : "v"(mLo));  // the wait for the atomic goes here
+    asm volatile("" : "+v"(baseAtomic) : "v"(mLo));  // the wait for the atomic goes here
     const uint32_t base = lane_value(baseAtomic, 0);
     if (pass) {  // lane q < 8 writes MPU q's entry
         const uint32_t slotq = qbase + base + (uint32_t)__popc(queue8 & ((1u << lane) - 1u));
@@ -1049,10 +1004,6 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
                 p.pqMask[2 * slotq + 1] = mHi;
             }
         }
-        // the MPU's octants proven uniform by the same bounds: k_mpu evaluates only the others
-        // (their inside bits are the proof's), bits 0-7 all outside, 8-15 all inside
-        if (PSGPU_S2_OCT)
-            p.pqOct[slotq] = (uint16_t)(((octOut >> (8 * lane)) & 0xffull) | (((octIn >> (8 * lane)) & 0xffull) << 8));
     }
     phase_stamp(p, 3, 8192u);
     if constexpr (FRONT) {
@@ -1068,11 +1019,12 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
 }
 
 #ifndef PSGPU_S2_N
-#define PSGPU_S2_N (8 / PSGPU_MPU_WAVES)  // x-slices per walk: one walk per (y,z) needle shares each
-                                          // primitive's uniform work and (y,z) terms over its points
+#define PSGPU_S2_N 8  // x-slices per walk: one walk per (y,z) needle shares each primitive's
+                      // uniform work and (y,z) terms over its points
 #endif
-// LDS per k_mpu block: per MPU of the block (4 / W of them): edgeVid[1536] u16 (passes 2-3) | cfg[344] u8 | vbase[344] u16 |
-// tbase[344] u16 | the 8 inside-bit words of the S2 cache | qv, qt; then per wave the
+// LDS per k_mpu block: per MPU of the block (4, or 2 with the tree split): edgeVid[1536] u16
+// (passes 2-3) | cfg[344] u8 | vbase[344] u16 | tbase[344] u16 | the 8 inside-bit words of the
+// S2 cache | a spare word, qt (the tree split's triangle base); then per wave the
 // interpreter's value slots.  The S2 field values never leave registers: pass 1 needs
 // only their inside bits (8 ballots, shared by the MPU's waves through LDS).
 constexpr int kLdsEdge = 0;
@@ -1098,8 +1050,8 @@ __device__ __forceinline__ int find_cell(const uint16_t* first, uint32_t r) {
     return lo;
 }
 
-// Barrier of the MPU's waves (the whole block when W > 1; LDS ordering within the wave
-// when one wave does it all).
+// Barrier of the MPU's waves (the whole block when the tree split gives an MPU two; LDS
+// ordering within the wave when one wave does it all).
 template <int WPM>
 __device__ __forceinline__ void mpu_sync() {
     if (WPM > 1) {
@@ -1110,90 +1062,12 @@ __device__ __forceinline__ void mpu_sync() {
     }
 }
 
-// S2 over the octants k_precheck could not prove uniform (bounds of the 4x4x4 corners
-// [4X, 4X+3] x [4Y, 4Y+3] x [4Z, 4Z+3], exactly the corner coordinates below): a pass walks up
-// to 4 octants, 16 lanes each -- lane (slot, yy, zz), a 4-point x-needle per lane -- so every
-// 4-lane pruning group is 4 z-consecutive corners z = 4Z..4Z+3 of one x and y, the
-// reference's S2 quads (:550-610), and every corner's value is the one the 8x8x8 walk gives.
-// Proven octants contribute their proof's inside bits.  ins[x] bit y*8 + z, as the 8-needle
-// layout's ballots; returned by lane 0 into sIns.
-template <int GROUP, class EV>
-__device__ __forceinline__ void s2_octants(const EV& ev, const float o[3], float cs, const CullMask& cm, uint32_t oct,
-                                           uint32_t U, int lane, uint64_t* sIns) {
-    uint64_t ins[8];
-#pragma unroll
-    for (int x = 0; x < 8; ++x) ins[x] = 0ull;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        if ((oct >> (8 + c)) & 1u) {  // octant c = X | Y << 1 | Z << 2 proven all inside
-            const uint64_t m = 0x0F0F0F0Full << (32 * ((c >> 1) & 1) + 4 * (c >> 2));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (c & 1) ins[4 + i] |= m;
-                else ins[i] |= m;
-            }
-        }
-    }
-    const int sl = lane >> 4, yy = (lane >> 2) & 3, zz = lane & 3;
-    uint32_t rest = U;
-#pragma unroll 1
-    while (rest != 0u) {
-        const uint32_t cur = rest;
-        // this lane's octant: the sl-th set bit of cur (a lane past the pass's octants repeats
-        // the first; its values are not used)
-        uint32_t cl = cur;
-        for (int j = 0; j < sl; ++j)
-            if (cl & (cl - 1u)) cl &= cl - 1u;
-            else cl = cur;
-        if (sl >= __popc(cur)) cl = cur;
-        const int c = __builtin_ctz(cl);
-        const int X = c & 1, Y = (c >> 1) & 1, Z = c >> 2;
-        float px[4], py[4], pz[4], f[4];
-        const float yv = o[1] + (float)(4 * Y + yy) * cs;
-        const float zv = o[2] + (float)(4 * Z + zz) * cs;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            px[i] = o[0] + (float)(4 * X + i) * cs;
-            py[i] = yv;
-            pz[i] = zv;
-        }
-        ev.template evaln<GROUP, false, 4>(px, py, pz, cm, f, nullptr);
-        uint32_t slots = cur;  // the pass's octants in slot order
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint64_t b = ballot(f[i] >= 0.5f);
-            uint32_t sc = slots;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if (sc == 0u) break;
-                const int cs_ = __builtin_ctz(sc);
-                sc &= sc - 1u;
-                const uint32_t bits = (uint32_t)(b >> (16 * s)) & 0xffffu;
-                const int Ys = (cs_ >> 1) & 1, Zs = cs_ >> 2;
-                uint64_t v = 0ull;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v |= (uint64_t)((bits >> (4 * r)) & 0xfu) << ((4 * Ys + r) * 8 + 4 * Zs);
-                if (cs_ & 1) ins[4 + i] |= v;
-                else ins[i] |= v;
-            }
-        }
-        // drop the pass's (up to) 4 octants
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (rest) rest &= rest - 1u;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x) sIns[x] = ins[x];
-    }
-}
-
-// Per-MPU body: W = kMpuWaves wavefronts per MPU that passed S1 (and was not proven
-// empty), 4 wavefronts per block.  Every wave of a block reaches every barrier: waves
-// without an MPU (past the last survivor) or whose MPU has no surface just skip the work.
+// Per-MPU body: one wavefront per MPU that passed S1 (and was not proven empty), 4
+// wavefronts per block.  Every wave of a block reaches every barrier: waves without an MPU
+// (past the last survivor) or whose MPU has no surface just skip the work.
 // SPLIT 2 (tree split): two waves per MPU, each walking one subtree of the root over all
 // 8 x-slices (evaln_part), the values exchanged through LDS and combined by both waves
-// (combine), which then share the record passes as the W > 1 x-slice split does.
+// (combine), which then share the record passes (batches of 64 records dealt in turn).
 // FRONT (k_front, the S2 blocks of the launch whose first p.preBlocks blocks run S1): block blk
 // takes entries [MPB * (blk >> 3), MPB * (blk >> 3) + MPB) of sub-queue blk & 7 as their S1
 // waves publish them (their ready words carry the run's tag), instead of the d-th survivor
@@ -1203,27 +1077,26 @@ template <class EV, int SPLIT = 1, bool FRONT = false>
 __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, uint32_t* item,
                                          const uint32_t blk = blockIdx.x) {
     *item = 0xffffffffu;
-    constexpr int WPM = SPLIT > 1 ? SPLIT : kMpuWaves;  // waves per MPU
-    constexpr int MPB = 4 / WPM;                         // MPUs per block
+    constexpr int WPM = SPLIT;     // waves per MPU
+    constexpr int MPB = 4 / SPLIT;  // MPUs per block
     const int wave = wave_index();
     const int lane = lane_id();
     const int slot = wave / WPM;  // the block's MPU this wave works on
-    const int part = wave % WPM;  // its share: x-slices [part * NX, part * NX + NX), or a subtree
-    constexpr int NX = SPLIT > 1 ? 8 : 8 / kMpuWaves;
-    // MPU d = block * (4 / W) + slot is the d-th queued survivor in shard order (dense over
-    // the 64 shard queues: lane s holds shard s's count); the grid is sized by the host
-    // from the last finished run, and a run with more survivors than that is re-run by finish()
+    const int part = wave % WPM;  // its subtree of the root (SPLIT 2), and its turn in the record passes
+    constexpr int NX = 8;         // x-slices of the S2 cache, all walked by this wave
     phase_stamp(p, 0);
     uint32_t d = blk * (uint32_t)MPB + (uint32_t)slot;
     ModelPtr M = as_const(p.model);
     const CubeTablesDev* tab = p.tables;  // global: L1 / L2 resident (an LDS copy per block measured slower, r05)
     bool live;
     uint32_t slotq = 0;
-    // PSGPU_BLOCK_RESERVE 1: the block's MPUs exchange their V (0 without surface) and arrive here
-    // after S3 pass 1; the last one reserves the block's vertex records with one atomic (zeroed
-    // before the prologue's barrier, which every wave of the block reaches)
+    // The block reserves its vertex records with one atomic into shard blk & 63, its MPUs back
+    // to back (the 64-record batches of k_vertex / k_finish then straddle MPUs of one S1 brick,
+    // whose live primitive sets overlap: DESIGN.md §4): the MPUs exchange their V (0 without
+    // surface) and arrive here after S3 pass 1, and the last one reserves (zeroed before the
+    // prologue's barrier, which every wave of the block reaches)
     __shared__ uint32_t sResV[MPB], sResArrive, sResBase;
-    if (PSGPU_BLOCK_RESERVE == 1 && threadIdx.x == 0) sResArrive = 0u;
+    if (threadIdx.x == 0) sResArrive = 0u;
     if constexpr (FRONT) {
         const uint32_t q = blk & 7u, e = (blk >> 3) * (uint32_t)MPB + (uint32_t)slot;
         d = (e << 3) | q;  // spreads the MPU's vertex records over the shards
@@ -1272,9 +1145,9 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
             sIncl[lane] = wave_incl_scan(cnt);
         }
         __syncthreads();
-        // MPU d = block * (4 / W) + slot is the d-th queued survivor in shard order (dense over
-        // the 64 shard queues); the grid is sized by the host from the last finished run, and
-        // a run with more survivors than that is re-run by finish()
+        // MPU d = block * MPB + slot is the d-th queued survivor in shard order (dense over
+        // the 64 shard queues: lane s holds shard s's count); the grid is sized by the host
+        // from the last finished run, and a run with more survivors than that is re-run by finish()
         const uint32_t incl = sIncl[lane];
         const uint32_t pcount = sIncl[kShards - 1];
         if (blk * (uint32_t)MPB >= pcount) return;  // whole block past the last survivor
@@ -1288,8 +1161,6 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     uint32_t m = 0, w = 0;
     float o[3] = {0.0f, 0.0f, 0.0f};
     CullMask cm{0ull, 0ull};
-    uint32_t oct = 0;  // k_precheck's octant proofs (PSGPU_S2_OCT)
-    (void)oct;
     if (live) {
         if (FRONT) {  // published in this launch: sc1 loads (the stores were sc1)
             m = uniform(__hip_atomic_load(&p.pq[slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -1298,26 +1169,18 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
                 cm.hi = uniform64(__hip_atomic_load(&p.pqMask[2 * slotq + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             }
         } else {
-        m = uniform(p.pq[slotq]);
-        if (p.cull) {  // the MPU box's culling mask, made by k_precheck: in SGPRs, so every
-                       // per-primitive culling test of the walk is a scalar branch
-#if PSGPU_UNIFORM_CM
-            cm.lo = uniform64(p.pqMask[2 * slotq]);
-            cm.hi = uniform64(p.pqMask[2 * slotq + 1]);
-#else
-            cm.lo = p.pqMask[2 * slotq];
-            cm.hi = p.pqMask[2 * slotq + 1];
-#endif
+            m = uniform(p.pq[slotq]);
+            if (p.cull) {  // the MPU box's culling mask, made by k_precheck: in SGPRs, so every
+                           // per-primitive culling test of the walk is a scalar branch
+                cm.lo = uniform64(p.pqMask[2 * slotq]);
+                cm.hi = uniform64(p.pqMask[2 * slotq + 1]);
+            }
         }
-        }
-        if (PSGPU_S2_OCT) oct = uniform((uint32_t)p.pqOct[slotq]);
         *item = m;
         w = m - p.mpuBegin;  // slot of the MPU in the range: counts / offsets index
         mpu_origin(p, m, o);
     }
     phase_stamp(p, 1);
-    // (block reservation: a wave without work still joins the block's barrier after pass 1)
-    if (PSGPU_BLOCK_RESERVE != 1 && WPM == 1 && !live) return;
     unsigned char* base = smem + slot * kLdsMpu;
     uint16_t* edgeVid = reinterpret_cast<uint16_t*>(base + kLdsEdge);
     uint8_t* cellCfg = base + kLdsCfg;
@@ -1330,8 +1193,8 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
 
     float fs[NX];
     if (live) {
-        // S2 (:550-610): corner (x, y, z) of the 8x8x8 cache, lane = y*8 + z, this wave's
-        // NX x-slices per lane; quads = 4 consecutive z
+        // S2 (:550-610): corner (x, y, z) of the 8x8x8 cache, lane = y*8 + z, the 8 x-slices
+        // per lane; quads = 4 consecutive z
         const int y = lane >> 3, z = lane & 7;
         const float py = o[1] + (float)y * cs;
         const float pz = o[2] + (float)z * cs;
@@ -1339,39 +1202,30 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
         float pxs[NX], pys[NX], pzs[NX];
 #pragma unroll
         for (int x = 0; x < NX; ++x) {
-            pxs[x] = o[0] + (float)((SPLIT > 1 ? 0 : part * NX) + x) * cs;  // SPLIT: both waves walk all 8
+            pxs[x] = o[0] + (float)x * cs;
             pys[x] = py;
             pzs[x] = pz;
         }
         if constexpr (SPLIT > 1) {
-            if (part == 0) ev.template evaln_part<kS2Group, false, 8, 0>(pxs, pys, pzs, cm, fs, nullptr);
-            else ev.template evaln_part<kS2Group, false, 8, 1>(pxs, pys, pzs, cm, fs, nullptr);
+            if (part == 0) ev.template evaln_part<4, false, 8, 0>(pxs, pys, pzs, cm, fs, nullptr);
+            else ev.template evaln_part<4, false, 8, 1>(pxs, pys, pzs, cm, fs, nullptr);
         } else {
-#if PSGPU_S2_OCT
-        const uint32_t U = ~(oct | (oct >> 8)) & 0xffu;  // octants without a proof
-        if (WPM == 1 && (PSGPU_S2_OCT == 2 || __popc(U) <= 4)) {
-            s2_octants<kS2Group>(ev, o, cs, cm, oct, U, lane, sIns);
-        } else {
-#else
-        {
-#endif
 #if PSGPU_S2_N == 1
-        // one walk per x-slice in a runtime loop: the walk's code stays resident in the
-        // instruction cache (unrolled copies of a 32-primitive walk do not fit)
+            // one walk per x-slice in a runtime loop: the walk's code stays resident in the
+            // instruction cache (unrolled copies of a 32-primitive walk do not fit)
 #pragma unroll 1
-        for (int h = 0; h < NX; ++h) fs[h] = ev.template eval<kS2Group, false>(pxs[h], py, pz, cm, nullptr);
+            for (int h = 0; h < NX; ++h) fs[h] = ev.template eval<4, false>(pxs[h], py, pz, cm, nullptr);
 #else
 #pragma unroll
-        for (int h = 0; h < NX; h += PSGPU_S2_N)
-            ev.template evaln<kS2Group, false, PSGPU_S2_N>(pxs + h, pys + h, pzs + h, cm, fs + h, nullptr);
+            for (int h = 0; h < NX; h += PSGPU_S2_N)
+                ev.template evaln<4, false, PSGPU_S2_N>(pxs + h, pys + h, pzs + h, cm, fs + h, nullptr);
 #endif
-        // inside bits of the 8x8x8 corners: ins[x] bit y*8 + z (lane order)
+            // inside bits of the 8x8x8 corners: ins[x] bit y*8 + z (lane order)
 #pragma unroll
-        for (int x = 0; x < NX; ++x) {
-            const uint64_t b = ballot(fs[x] >= 0.5f);
-            if (lane == 0) sIns[part * NX + x] = b;
-        }
-        }
+            for (int x = 0; x < NX; ++x) {
+                const uint64_t b = ballot(fs[x] >= 0.5f);
+                if (lane == 0) sIns[x] = b;
+            }
         }
     }
     uint64_t ins[8];
@@ -1403,18 +1257,17 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
             for (int x = 0; x < 8; ++x) ins[x] = 0ull;
         }
     } else {
-    phase_stamp(p, 3);
-    mpu_sync<WPM>();
-    phase_stamp(p, 4);
+        phase_stamp(p, 3);
+        mpu_sync<WPM>();
+        phase_stamp(p, 4);
 #pragma unroll
-    for (int x = 0; x < 8; ++x) {
-        ins[x] = live ? sIns[x] : 0ull;
-        inside += __popcll(ins[x]);
-    }
+        for (int x = 0; x < 8; ++x) {
+            ins[x] = live ? sIns[x] : 0ull;
+            inside += __popcll(ins[x]);
+        }
     }
     const bool work = live && inside != 0 && inside != 512 && !(p.debug & 1u);
     if (live && !work && part == 0 && lane == 0) p.counts[w] = 0ull;  // no vertices, no triangles
-    if (PSGPU_BLOCK_RESERVE != 1 && WPM == 1 && !work) return;
 
     // S3 pass 1 (:647-691): config per cell (bit c = x*4 + y*2 + z, inside = f >= 0.5),
     // owned sign-changing edges (new vertices) and triangles; wave prefix sums give
@@ -1423,10 +1276,10 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     // Every wave of the MPU computes V and T; the first writes the tables and counters.
     const uint64_t edgeBits = tab->edge;
     uint32_t V = 0, T = 0;
-    // WPM 1: the record queues' bases stay in lane 0's registers (the returning atomics are not
-    // waited for until pass 2 stores its first record: their round trip overlaps the record's
-    // cell search; verdict r05 item 4: the record passes hold half of k_mpu's parked cycles)
-    uint32_t qvAtomic = 0u, qtAtomic = 0u;
+    // WPM 1: the triangle queue's base stays in lane 0's registers (the returning atomic is not
+    // waited for until pass 3 reads it: its round trip overlaps pass 2; verdict r05 item 4: the
+    // record passes hold half of k_mpu's parked cycles)
+    uint32_t qtAtomic = 0u;
     if (work) {
         uint32_t carry = 0;  // V | T << 16 (both <= 343 * 12 per MPU: no carry between the halves)
         const int j = lane >> 3, k = lane & 7;
@@ -1460,13 +1313,8 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
         if (part == 0) {
             const uint32_t shard = d & (kShards - 1);
             if (lane == 0) {
-                if (PSGPU_BLOCK_RESERVE != 1)
-                    qvAtomic = atomicAdd(&p.ctr->shard[PSGPU_BLOCK_RESERVE ? blk & (kShards - 1) : shard].v, V);
                 qtAtomic = atomicAdd(&p.ctr->shard[w & (kShards - 1)].t, T);  // TriRec: shard = w & 63
-                if (WPM > 1) {
-                    sQ[0] = qvAtomic;
-                    sQ[1] = qtAtomic;
-                }
+                if (WPM > 1) sQ[1] = qtAtomic;
                 p.counts[w] = (uint64_t)V | ((uint64_t)T << 32);
                 if (T > 0) atomicAdd(&p.ctr->shard[shard].s, 1u);
                 if (V > 512u || T > 512u) atomicMin(&p.ctr->firstOverflow, (int)m);
@@ -1484,29 +1332,24 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     }
 #endif
     const bool recs = work && !(p.debug & 2u);  // ablation bit 1: pass 1 only
-    if (PSGPU_BLOCK_RESERVE == 1) {
-        // the block's rendezvous: every MPU leaves its V in slot order and counts itself in; the
-        // last to arrive has all of them and reserves their sum in shard blk & 63.  Its wait for
-        // the atomic is the block's: the base is published at the barrier (making each wave's
-        // first batch of records before the barrier, to hide that wait, measured the same:
-        // profiles/r07_block_reserve_ab.txt)
-        if (part == 0 && lane == 0) {
-            sResV[slot] = V;
-            if (__hip_atomic_fetch_add(&sResArrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) ==
-                (uint32_t)MPB - 1u) {
-                uint32_t sum = 0;
+    // the block's rendezvous: every MPU leaves its V in slot order and counts itself in; the
+    // last to arrive has all of them and reserves their sum in shard blk & 63.  Its wait for
+    // the atomic is the block's: the base is published at the barrier (making each wave's
+    // first batch of records before the barrier, to hide that wait, measured the same:
+    // profiles/r07_block_reserve_ab.txt)
+    if (part == 0 && lane == 0) {
+        sResV[slot] = V;
+        if (__hip_atomic_fetch_add(&sResArrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) ==
+            (uint32_t)MPB - 1u) {
+            uint32_t sum = 0;
 #pragma unroll
-                for (int k = 0; k < MPB; ++k) sum += sResV[k];
-                sResBase = sum ? atomicAdd(&p.ctr->shard[blk & (kShards - 1)].v, sum) : 0u;
-            }
+            for (int k = 0; k < MPB; ++k) sum += sResV[k];
+            sResBase = sum ? atomicAdd(&p.ctr->shard[blk & (kShards - 1)].v, sum) : 0u;
         }
-        __syncthreads();
-        if (WPM == 1 && !work) return;
-    } else {
-        mpu_sync<WPM>();
     }
-    const uint32_t shard = d & (kShards - 1);
-    VertexKey* vk = p.vk + (size_t)(PSGPU_BLOCK_RESERVE ? blk & (kShards - 1) : shard) * p.vShardCap;
+    __syncthreads();
+    if (WPM == 1 && !work) return;
+    VertexKey* vk = p.vk + (size_t)(blk & (kShards - 1)) * p.vShardCap;
     TriRec* tq = p.tq + (size_t)(w & (kShards - 1)) * p.tShardCap;
 
     // pass 2 (:703-762), one lane per new vertex r (batches of 64 dealt to the MPU's waves
@@ -1514,13 +1357,10 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     // k-th owned crossing edge in first-occurrence order of the row, k = r - first id.
     // Records are written coalesced.
     if (recs) {
-        uint32_t qv = WPM > 1 ? sQ[0] : 0u;
-        if (PSGPU_BLOCK_RESERVE == 1) {  // the block's base + the V of its earlier slots
-            qv = sResBase;
+        uint32_t qv = sResBase;  // the block's base + the V of its earlier slots
 #pragma unroll
-            for (int k = 0; k < MPB - 1; ++k)
-                if (k < slot) qv += sResV[k];
-        }
+        for (int k = 0; k < MPB - 1; ++k)
+            if (k < slot) qv += sResV[k];
         for (uint32_t b0 = (uint32_t)part * 64u; b0 < V; b0 += 64u * WPM) {
             const uint32_t r = b0 + (uint32_t)lane;
             if (r < V) {
@@ -1543,12 +1383,6 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
                 const int sx = i + ((c1 >> 2) & 1), sy = j + ((c1 >> 1) & 1), sz = k + (c1 & 1);
                 edgeVid[((sx * 8 + sy) * 8 + sz) * 3 + ax] = (uint16_t)r;
                 const uint32_t key = (uint32_t)sx | ((uint32_t)sy << 3) | ((uint32_t)sz << 6) | ((uint32_t)ax << 9);
-                if (WPM == 1 && PSGPU_BLOCK_RESERVE != 1) {  // lane 0's atomic result, read only once the record
-                                                             // is made (the empty asm ties the read, and the
-                                                             // wait for the atomic, to the key)
-                    if (PSGPU_DEFER_ATOMICS) asm volatile("" : "+v"(qvAtomic) : "v"(key));
-                    qv = lane_value(qvAtomic, 0);
-                }
                 const uint32_t g = qv + r;
                 if (g < p.vShardCap) vk[g] = VertexKey{w, r | (key << 16)};
             }
@@ -1769,27 +1603,6 @@ __device__ __forceinline__ void scan_counts_block(const Params& p, uint32_t b) {
     }
 }
 
-// Cull mask for the AABB of N points per lane (all 64 lanes must participate),
-// grown by `ext` on the high side of every axis.
-template <int N>
-__device__ __forceinline__ CullMask cull_mask_points_n(ModelPtr M, const float* px, const float* py, const float* pz,
-                                                       bool enable, float ext = 0.0f) {
-    if (!enable) return CullMask{0ull, 0ull};
-    bool nan = false;
-    float x0 = px[0], x1 = px[0], y0 = py[0], y1 = py[0], z0 = pz[0], z1 = pz[0];
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        nan = nan || !(px[n] == px[n]) || !(py[n] == py[n]) || !(pz[n] == pz[n]);
-        x0 = fminf(x0, px[n]); x1 = fmaxf(x1, px[n]);
-        y0 = fminf(y0, py[n]); y1 = fmaxf(y1, py[n]);
-        z0 = fminf(z0, pz[n]); z1 = fmaxf(z1, pz[n]);
-    }
-    // a NaN coordinate (fminf/fmaxf would hide it) disables culling for the wave
-    if (ballot(nan) != 0ull) return CullMask{0ull, 0ull};
-    return cull_mask_box(M, wave_min(x0), wave_min(y0), wave_min(z0), wave_max(x1) + ext, wave_max(y1) + ext,
-                         wave_max(z1) + ext);
-}
-
 // Culling mask of a wave whose lanes hold points of the MPUs w (range slots): the AND of
 // those MPUs' masks (k_mpu, box grown by the normal delta), one scalar load pair per
 // distinct MPU.  A primitive culled for every one of the boxes is +0 at all the points.
@@ -1842,18 +1655,13 @@ __device__ __forceinline__ void vertex_root(const EdgeSeg& E, uint32_t iv, float
     }
 }
 
-#ifndef PSGPU_V_N
-#define PSGPU_V_N 1  // vertices per quad of lanes per k_vertex pass (2: bigger culling boxes, slower)
-#endif
-
-// Vertices: 16 * VN per wavefront pass, one quad of lanes per vertex and VN vertices
-// per quad (vertex first + quad + 16n), each walk evaluating VN points per lane.
+// Vertices: 16 per wavefront pass, one quad of lanes per vertex (vertex first + quad), each
+// walk evaluating one point per lane.
 // Quad pruning: the 4 edge samples e1 + (e2-e1)*(l/3), l = 0..3 (:722-762), then the
 // linear root.  The position goes into the vertex record; k_finish evaluates value,
 // colour and normal there (:764-807) and places the vertex in the mesh.
 template <class EV, int VPW = 16>
 __device__ __forceinline__ void vertex_body(const Params& p, float* lds) {
-    constexpr int VN = PSGPU_V_N;
     const int wave = wave_index();
     const int lane = lane_id();
     ModelPtr M = as_const(p.model);
@@ -1903,98 +1711,44 @@ if constexpr (VPW == 64) {
         if (valid) p.vp[rec] = VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
     }
 } else {
-    const ShardBatches sb(sCnt, p.vShardCap, 16 * VN);
+    const ShardBatches sb(sCnt, p.vShardCap, 16);
     for (uint32_t batch = blockIdx.x * (blockDim.x >> 6) + wave; batch < sb.total; batch += nWaves) {
         uint32_t shard, first, count;
         sb.locate(batch, &shard, &first, &count);
-        bool valid[VN];
-        size_t rec[VN];
-        float qx[VN], qy[VN], qz[VN];
-        uint32_t wrec[VN];
-#pragma unroll
-        for (int n = 0; n < VN; ++n) {
-            uint32_t rr = first + ((uint32_t)lane >> 2) + 16u * (uint32_t)n;
-            valid[n] = rr < count;
-            if (!valid[n]) rr = first;
-            rec[n] = (size_t)shard * p.vShardCap + rr;
-            const VertexKey R = p.vk[rec[n]];
-            wrec[n] = R.w;
-            const EdgeSeg E = edge_segment(p, R.w, R.vidKey >> 16);
-            qx[n] = edge_sample(E.e[0], E.d[0], j);  // lane j of the quad: sample j
-            qy[n] = edge_sample(E.e[1], E.d[1], j);
-            qz[n] = edge_sample(E.e[2], E.d[2], j);
-        }
+        uint32_t rr = first + ((uint32_t)lane >> 2);
+        const bool valid = rr < count;
+        if (!valid) rr = first;
+        const size_t rec = (size_t)shard * p.vShardCap + rr;
+        const VertexKey R = p.vk[rec];
+        const EdgeSeg E = edge_segment(p, R.w, R.vidKey >> 16);
+        const float qx = edge_sample(E.e[0], E.d[0], j);  // lane j of the quad: sample j
+        const float qy = edge_sample(E.e[1], E.d[1], j);
+        const float qz = edge_sample(E.e[2], E.d[2], j);
         // every edge sample lies in its MPU's box (k_mpu's mask; the d^2 >= 1.02 margin
         // absorbs the last-bit rounding of e1 + cs vs lo + 7 cs)
         CullMask cm{0ull, 0ull};
-        if (p.cull) {
-            if (VN == 1) {
-                cm = cull_mask_mpus(p, wrec[0]);
-            } else {
-                cm = cull_mask_points_n<VN>(M, qx, qy, qz, true);
-            }
-        }
-        float f[VN];
+        if (p.cull) cm = cull_mask_mpus(p, R.w);
+        float f;
         if (p.debug & 256u) {  // ablation bit 8: no phase-A walk
-#pragma unroll
-            for (int n = 0; n < VN; ++n) f[n] = qx[n];
+            f = qx;
         } else {
-            ev.template evaln<4, false, VN>(qx, qy, qz, cm, f, nullptr);
+            ev.template evaln<4, false, 1>(&qx, &qy, &qz, cm, &f, nullptr);
         }
-#pragma unroll
-        for (int n = 0; n < VN; ++n) {
-            float fs[4];
-            fs[0] = quad_bcast<0>(f[n]);
-            fs[1] = quad_bcast<1>(f[n]);
-            fs[2] = quad_bcast<2>(f[n]);
-            fs[3] = quad_bcast<3>(f[n]);
-            // first sample whose inside state differs from sample 0, else 3 (:744-755)
-            const bool st0 = fs[0] >= 0.5f;
-            const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
-            const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
-            const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
-            // into the record; k_finish recomputes the root there (vertex_root) and adds
-            // normal and colour
-            if (valid[n] && j == 0) p.vp[rec[n]] = VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
-        }
+        float fs[4];
+        fs[0] = quad_bcast<0>(f);
+        fs[1] = quad_bcast<1>(f);
+        fs[2] = quad_bcast<2>(f);
+        fs[3] = quad_bcast<3>(f);
+        // first sample whose inside state differs from sample 0, else 3 (:744-755)
+        const bool st0 = fs[0] >= 0.5f;
+        const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
+        const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
+        const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
+        // into the record; k_finish recomputes the root there (vertex_root) and adds
+        // normal and colour
+        if (valid && j == 0) p.vp[rec] = VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
     }
 }
-}
-
-#ifndef PSGPU_FIN_TRI_PREFETCH
-#define PSGPU_FIN_TRI_PREFETCH 0  // measured neutral (isolated k_finish 27.8 us either way, r05)
-#endif
-// One lane's triangle record of a k_finish batch and its MPU's (V | T << 32) offset: the
-// global triangle gt = T offset + local id, its corners = V offset + local vertex ids (S6,
-// PS_Polygonizer.cpp:816-825, in the compact mesh's MPU order).
-struct TriPre {
-    TriRec R;
-    uint64_t o;
-    bool ok;
-};
-__device__ __forceinline__ TriPre tri_load(const Params& p, const ShardBatches& sb, uint32_t batch) {
-    TriPre t;
-    t.ok = false;
-    t.R = TriRec{0u, 0u};
-    t.o = 0ull;
-    if (batch >= sb.total) return t;
-    uint32_t shard, first, count;
-    sb.locate(batch, &shard, &first, &count);
-    const uint32_t i = first + lane_id();
-    if (i >= count) return t;
-    t.R = p.tq[(size_t)shard * p.tShardCap + i];
-    t.o = p.offs[((t.R.a >> 12) << 6) | shard];  // the record's shard is w & 63
-    t.ok = true;
-    return t;
-}
-__device__ __forceinline__ void tri_store(const Params& p, const TriPre& t) {
-    if (!t.ok) return;
-    const uint32_t gt = (uint32_t)(t.o >> 32) + (t.R.a & 2047u);
-    const uint32_t base = (uint32_t)t.o;
-    if (gt >= p.tCap) return;  // finish() grows and re-runs
-    p.tris[gt * 3 + 0] = base + (t.R.b & 2047u);
-    p.tris[gt * 3 + 1] = base + ((t.R.b >> 11) & 2047u);
-    p.tris[gt * 3 + 2] = base + ((t.R.b >> 22) | (((t.R.a >> 11) & 1u) << 10));
 }
 
 // Finish: per vertex fieldValueAndColor's value and colour walk (PS_Polygonizer.cpp:777-778,
@@ -2041,12 +1795,6 @@ __device__ __forceinline__ void finish_body(const Params& p, float* lds) {
     stage_shard_counts(p, 1, sCnt);            // ShardCtr::v
     stage_shard_counts(p, 2, sCnt + kShards);  // ShardCtr::t
     __syncthreads();
-#if PSGPU_FIN_TRI_PREFETCH
-    // the wave's first triangle batch loaded before the vertex walk: its records and their
-    // MPUs' offsets do not depend on the walk, so their two dependent loads overlap it
-    const ShardBatches sbp(sCnt + kShards, p.tShardCap, 64);
-    const TriPre tp0 = tri_load(p, sbp, wave0);
-#endif
     phase_stamp_after(p, 1, 2048u, 0.0f);
 if constexpr (VPW == 16) {
     // a quad of lanes per vertex: lane j of the quad walks point j (p, p + delta e_x,
@@ -2239,12 +1987,7 @@ if constexpr (VPW == 16) {
 }
     if (p.debug & 64u) return;  // ablation bit 6: no triangles
     const ShardBatches sb(sCnt + kShards, p.tShardCap, 64);
-    uint32_t batch0 = wave0;
-#if PSGPU_FIN_TRI_PREFETCH
-    tri_store(p, tp0);
-    batch0 += nWaves;
-#endif
-    for (uint32_t batch = batch0; batch < sb.total; batch += nWaves) {
+    for (uint32_t batch = wave0; batch < sb.total; batch += nWaves) {
         uint32_t shard, first, count;
         sb.locate(batch, &shard, &first, &count);
         const uint32_t t = first + lane;

@@ -434,17 +434,6 @@ size_t brick_count(const psgpu_ctx* c) {
     return (size_t)bd[0] * bd[1] * bd[2];
 }
 
-// The S2-by-octants experiment (PSGPU_S2_OCT, off by default, measured slower: DESIGN.md §4)
-// is compiled in only through PSGPU_JIT_FLAGS; its per-entry proof words exist only then.
-bool s2_oct_enabled() {
-    static const bool on = [] {
-        const char* f = getenv("PSGPU_JIT_FLAGS");
-        const char* d = f ? strstr(f, "PSGPU_S2_OCT=") : nullptr;
-        return d != nullptr && d[13] != '\0' && d[13] != '0';
-    }();
-    return on;
-}
-
 // k_front sub-queue capacity for a k_precheck grid of `blocks` blocks of `mpb` bricks: every
 // 8th block's bricks x 8 MPUs; front_cap(bricks) bounds it for both grids (2 and 4 bricks per block)
 uint32_t front_sub_cap(uint32_t blocks, uint32_t mpb) { return 8u * mpb * ((blocks + 7u) / 8u); }
@@ -465,7 +454,6 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
         PSGPU_CHECK(grow(c->fqReady, c->capFq, fq));
         PSGPU_CHECK(hipMemset(c->fqReady, 0, c->capFq * sizeof(uint32_t)));
     }
-    if (s2_oct_enabled()) PSGPU_CHECK(grow(c->pqOct, c->capPqOct, (size_t)c->pShardCap * kShards));
     PSGPU_CHECK(grow(c->counts, c->capCounts, n));
     PSGPU_CHECK(grow(c->passed, c->capPassed, n));
     PSGPU_CHECK(grow(c->mpuMasks, c->capMasks, 2 * n));
@@ -529,7 +517,6 @@ Params make_params(psgpu_ctx* c) {
     p.brickStride = brick_stride((uint32_t)brick_count(c), (c->debug & 16384) != 0);
     p.pq = c->pq;
     p.pqMask = c->pqMask;
-    p.pqOct = c->pqOct;
     p.pShardCap = c->pShardCap;
     // k_mpu: one wave per queued survivor, as many as the last finished run queued + 1/4
     // (a run that queues more is re-run by finish(): the grid then fits exactly)
@@ -917,9 +904,7 @@ void reset_run_state(psgpu_ctx* c) {
 // ===========================================================================
 extern "C" {
 
-#define PSGPU_STR2(x) #x
-#define PSGPU_STR(x) PSGPU_STR2(x)
-const char* psgpu_version(void) { return "parsip_amd 0.1 (gfx950, block reserve " PSGPU_STR(PSGPU_BLOCK_RESERVE) ")"; }
+const char* psgpu_version(void) { return "parsip_amd 0.1 (gfx950)"; }
 
 void psgpu_tritable(int32_t out[256 * 16]) {
     const CubeTables& T = cube_tables();
@@ -1157,7 +1142,7 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->jit.reset();
     c->jit1.reset();
     weld_free(c);
-    void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->pqOct, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
+    void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
                     c->pos, c->nrm, c->col, c->tris, c->ctr, c->totals, c->stamps, c->spans, c->mpuTicks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);

@@ -191,23 +191,8 @@ struct DevCounters {
     ShardCtr shard[kShards];
 };
 
-#ifndef PSGPU_MPU_WAVES
-#define PSGPU_MPU_WAVES 1  // waves per S1 survivor in k_mpu (1, 2 or 4): each walks 8 / W of the
-                           // 8 x-slices of the S2 cache and takes every W-th batch of records,
-                           // so a heavy MPU's critical path is ~1/W of one wave doing it all.
-                           // Host and device must agree (build.py and the JIT pass the same value).
-                           // C3 ms/step on one box: W=1 0.0624, W=2 0.0669, W=4 0.0722.
-#endif
-#ifndef PSGPU_BLOCK_RESERVE
-#define PSGPU_BLOCK_RESERVE 1  // k_mpu's vertex-queue reservations: 0 one per MPU into shard d & 63;
-                               // 1 one per block into shard blk & 63, the block's MPUs back to back
-                               // (the 64-record batches of k_vertex / k_finish then straddle MPUs of
-                               // one S1 brick, whose live primitive sets overlap: DESIGN.md §4);
-                               // 2 one per MPU, all of a block's into shard blk & 63.  The JIT passes
-                               // the library's value on (build.py: PSGPU_BLOCK_RESERVE=<n> for A/B).
-#endif
-constexpr int kMpuWaves = PSGPU_MPU_WAVES;
-constexpr int kMpusPerBlock = 4 / kMpuWaves;  // k_mpu blocks are 4 waves
+constexpr int kMpusPerBlock = 4;  // k_mpu blocks are 4 waves, one per queued S1 survivor (2 per
+                                  // survivor in the tree-split kernels: 2 survivors per block)
 constexpr int kNumStampKernels = 4;  // k_precheck, k_mpu, k_vertex, k_finish
 constexpr int kSpanLanes = 64;       // {min start, max end} pairs per kernel per run (PSGPU_OPT_SPANS)
 
@@ -230,7 +215,6 @@ struct Params {
                             // permutation that spreads the surface's heavy bricks over the CUs)
     uint32_t* pq;           // kShards queues of pShardCap S1 survivors (global MPU ids)
     uint64_t* pqMask;       // per queue entry: the MPU box's culling mask (2 words, by k_precheck)
-    uint16_t* pqOct;        // per queue entry: octants proven all outside (bits 0-7) / inside (8-15)
     uint32_t pShardCap;     // 8 * ceil(precheck waves / kShards): cannot overflow
     uint32_t* fqReady;      // k_front: per queue entry, the run's tag once the entry is published
     uint32_t fqCap;         // k_front: entries per sub-queue (8 sub-queues at pq + k * fqCap)

@@ -1,11 +1,10 @@
-"""k_mpu's block-level reservation of the vertex record queue (PSGPU_BLOCK_RESERVE, psgpu_model.h):
+"""k_mpu's block-level reservation of the vertex record queue (mpu_body, psgpu_device.h):
 the mesh stays the oracle's bit for bit whatever a block holds (partial blocks, MPUs without a
 surface among MPUs with one, shards that overflow), the queue stays dense and contiguous per MPU,
 a block's MPUs lie back to back in one shard, and the 64-record batches of the vertex walks then
 see fewer live primitives (tools/batch_live.py on the queue the GPU wrote)."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -23,16 +22,12 @@ NONE = 0xFFFFFFFF
 STAMP_WAVES = 1 << 18  # k_mpu waves recorded: more than any grid of C2 / C3
 
 # Live primitives per 64-record batch (vertex-weighted mean, tools/batch_live.py) of the C3 queue
-# the parent commit's per-MPU reservation writes (PSGPU_BLOCK_RESERVE=0 build of this tree, the
-# same kernels), measured on an MI355X, 2026-10-19 (k_front's queue order keeps some neighbours
-# together: the CPU model gives 6.46 for unrelated neighbours) and the model's value for one
-# reservation per block.
+# the earlier per-MPU reservation wrote (one reservation per MPU into shard d & 63, the kernels
+# otherwise the same; commit 3e38f9d is the last tree that compiles that variant), measured on
+# an MI355X, 2026-10-19 (k_front's queue order keeps some neighbours together: the CPU model
+# gives 6.46 for unrelated neighbours) and the model's value for one reservation per block.
 PARENT_C3_MEAN_LIVE = 6.01
 MODEL_BLOCK_MEAN_LIVE = 4.80
-
-
-def reserve_mode() -> int:
-    return int(re.search(r"block reserve (\d)", gpu.load().psgpu_version().decode()).group(1))
 
 
 @pytest.fixture(scope="module")
@@ -166,9 +161,6 @@ def check_queue(info, counts, shards, blocks, om, mpb):
             assert m not in where, f"MPU {m} in two places"
             where[int(m)] = (s, int(a))
     assert sorted(where) == list(np.flatnonzero(V))
-    mode = reserve_mode()
-    if mode == 0:
-        return
     grouped = 0
     for blk, row in enumerate(blocks):
         mpus = list(dict.fromkeys(int(m) for m in row if m != NONE))  # slot order; two waves per MPU with the split
@@ -176,9 +168,8 @@ def check_queue(info, counts, shards, blocks, om, mpb):
         mpus = [m for m in mpus if V[m] > 0]
         for m in mpus:
             assert where[m][0] == blk % 64, (blk, m, where[m])
-        if mode == 1:  # one reservation: the block's MPUs back to back, in slot order
-            for m0, m1 in zip(mpus, mpus[1:]):
-                assert where[m1][1] == where[m0][1] + V[m0], (blk, mpus)
+        for m0, m1 in zip(mpus, mpus[1:]):  # one reservation: the block's MPUs back to back, in slot order
+            assert where[m1][1] == where[m0][1] + V[m0], (blk, mpus)
         grouped += len(mpus)
     assert grouped == len(where)  # every MPU with records was some block's
 

@@ -10,7 +10,7 @@ isolated timeline of one polygonization.
 
 Usage (GPU): python tools/engines_timeline.py [--engines 4] [--config C3] [--json out.json]
 (--engines 1: one context, its last run alone.)
-The environment selects kernel variants (e.g. PSGPU_JIT_FLAGS=-DPSGPU_S2_GROUP=5).
+The environment selects kernel variants (e.g. PSGPU_JIT_FLAGS=-DPSGPU_FIN_PHASES=1).
 """
 import argparse
 import ctypes
