@@ -315,6 +315,12 @@ int  psgpu_download_stamps(psgpu_ctx* ctx, uint64_t* out, uint32_t* cap);
  * the range, MPU-local vertex id), shard after shard in queue order: 2 x sum(counts) words.
  * capacity is in records; PSGPU_RET_PARAM_ERROR if it is short (counts is still written). */
 int  psgpu_vertex_queue(psgpu_ctx* ctx, uint32_t* counts, uint32_t* recs, uint32_t capacity);
+/* Debug export of the finished run's per-MPU masks (tests): for each of the range's ctMPUs,
+ * queued[w] = 1 if k_precheck queued the MPU for S2 (only those have masks) and masks[4 w ..
+ * 4 w + 3] = its culling mask (2 words, bit i: primitive i) and its op-inside mask (2 words,
+ * bit k: op k; PSGPU_OPT_OP_INSIDE), zeros for an MPU that was not queued or a run without
+ * culling.  capacity is in MPUs; PSGPU_RET_PARAM_ERROR if it is short. */
+int  psgpu_mpu_masks(psgpu_ctx* ctx, uint8_t* queued, uint64_t* masks, uint32_t capacity);
 /* PrintThreadResults (PS_Polygonizer.h:393, body .cpp:414-428, counters .cpp:443-469).
  * The reference keeps one (processed, crossed) MPU count pair per TBB worker that ran an
  * MPU, accumulated over every Polygonize of the process.  Here the worker is a device
@@ -345,6 +351,11 @@ int  psgpu_download_spans(psgpu_ctx* ctx, uint64_t* out, uint32_t* runs);
 int  psgpu_set_option(psgpu_ctx* ctx, int option, int64_t value);
 #define PSGPU_OPT_KERNEL_TIMING 1   /* 1: record hipEvents around every kernel */
 #define PSGPU_OPT_CULLING       2   /* 1: exact per-wave primitive culling (default) */
+#define PSGPU_OPT_OP_INSIDE    23   /* 1 (default): k_precheck makes, beside each queued MPU's culling
+                                       mask, a mask of the ops whose box holds the MPU's box along
+                                       one axis; the specialised walks skip those ops' pruning tests
+                                       (which cannot prune there).  0: zero masks, every test runs.
+                                       Identical output; needs PSGPU_OPT_CULLING */
 #define PSGPU_OPT_DEBUG         9   /* profiling ablations (bit 0: stop after S2); 0 in use;
                                        bit 20 (test hook): the next run's k_mpu grid is one
                                        block, so finish must re-run it with the full grid;

@@ -354,9 +354,18 @@ __device__ __forceinline__ bool op_colour_weights(uint32_t type, float lf, float
 // infinite axis (where the reference's sqrt of a rounded-negative value is NaN).  The
 // margin d^2 >= 1.02 covers fp32 rounding of the reference formulas by orders of
 // magnitude.  Triangle is a constant +0 (dist2 = FLT_MAX) and is always culled.
+// inLo / inHi: the op-inside mask that rides with it (op_inside_box, psgpu_model.h): bit k set
+// means every point of the wave lies inside op k's box along one axis, so op k's pruning test
+// cannot prune and the generated walks skip it.  Made per queued MPU by k_precheck only; every
+// other source of a CullMask (the wave's own box: S1, k_finish's off-segment fallback, the
+// probe) leaves it 0, where every test runs.
 struct CullMask {
     uint64_t lo, hi;
+    uint64_t inLo, inHi;
 };
+__device__ __forceinline__ bool op_inside(const CullMask& cm, uint32_t k) {
+    return k < 64 ? ((cm.inLo >> k) & 1ull) : ((cm.inHi >> (k - 64)) & 1ull);
+}
 
 // This lane's culling segments (prims `lane` and 64 + `lane`), loaded once and early: the
 // loads do not depend on the box, so they overlap the rest of a kernel's prologue.
@@ -967,23 +976,45 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     // with the queue entry, for S2 (k_mpu loads no culling data).  The grown box contains the
     // S2 box, so its mask is conservative there too; one mask per MPU instead of two (the
     // boxes differ by 0.001: the masks are the same but for primitives grazing the box).
-    uint64_t mLo = 0ull, mHi = 0ull;  // lane q < 8: MPU q's mask, for its queue entry
+    // Beside it the MPU's op-inside mask (op_inside_box; its own margin, no culling slack),
+    // lane-parallel over the ops as the culling mask is over the primitives: lane i holds the
+    // boxes of ops i and 64 + i, one ballot per word.  PSGPU_OPT_OP_INSIDE 0: zero masks.
+    uint64_t mLo = 0ull, mHi = 0ull, iLo = 0ull, iHi = 0ull;  // lane q < 8: MPU q's masks, for its queue entry
     if (p.cull) {
         const float eg = 7.0f * p.cs + 0.001f;
+        ModelPtr Mo = as_const(p.model);
+        const uint32_t nOps = p.opInside ? Mo->ctOps : 0u;
+        float bl[2][3], bh[2][3];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint32_t k = 64u * h + (uint32_t)lane;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {  // past ctOps: an empty box, inside of nothing
+                bl[h][a] = k < nOps ? p.model->ops[k].lo[a] : 1.0f;
+                bh[h][a] = k < nOps ? p.model->ops[k].hi[a] : -1.0f;
+            }
+        }
         for (uint32_t qm = queue8; qm != 0u; qm &= qm - 1u) {
             const int q = __builtin_ctz(qm);
             const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[0]), 8 * q));
             const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[1]), 8 * q));
             const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[2]), 8 * q));
-            const CullMask g = cull_mask_from(cl, ox, oy, oz, ox + eg, oy + eg, oz + eg);
+            CullMask g = cull_mask_from(cl, ox, oy, oz, ox + eg, oy + eg, oz + eg);
+            if (nOps != 0u) g.inLo = ballot((uint32_t)lane < nOps && op_inside_box(bl[0], bh[0], ox, oy, oz, p.cs));
+            if (nOps > 64u)
+                g.inHi = ballot(64u + (uint32_t)lane < nOps && op_inside_box(bl[1], bh[1], ox, oy, oz, p.cs));
             const uint32_t wq = lane_value(mOf, q) - p.mpuBegin;
             if (lane == 0) {
-                p.mpuMasks[2 * wq] = g.lo;
-                p.mpuMasks[2 * wq + 1] = g.hi;
+                p.mpuMasks[4 * wq] = g.lo;
+                p.mpuMasks[4 * wq + 1] = g.hi;
+                p.mpuMasks[4 * wq + 2] = g.inLo;
+                p.mpuMasks[4 * wq + 3] = g.inHi;
             }
             if (lane == q) {
                 mLo = g.lo;
                 mHi = g.hi;
+                iLo = g.inLo;
+                iHi = g.inHi;
             }
         }
     }
@@ -994,14 +1025,18 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
         if (FRONT) {  // read in this launch by S2 waves on other CUs: write-through (sc1)
             __hip_atomic_store(&p.pq[slotq], mOf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (p.cull) {
-                __hip_atomic_store(&p.pqMask[2 * slotq], mLo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&p.pqMask[2 * slotq + 1], mHi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&p.pqMask[4 * slotq], mLo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&p.pqMask[4 * slotq + 1], mHi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&p.pqMask[4 * slotq + 2], iLo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&p.pqMask[4 * slotq + 3], iHi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         } else {
             p.pq[slotq] = mOf;
             if (p.cull) {
-                p.pqMask[2 * slotq] = mLo;
-                p.pqMask[2 * slotq + 1] = mHi;
+                p.pqMask[4 * slotq] = mLo;
+                p.pqMask[4 * slotq + 1] = mHi;
+                p.pqMask[4 * slotq + 2] = iLo;
+                p.pqMask[4 * slotq + 3] = iHi;
             }
         }
     }
@@ -1165,15 +1200,21 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
         if (FRONT) {  // published in this launch: sc1 loads (the stores were sc1)
             m = uniform(__hip_atomic_load(&p.pq[slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             if (p.cull) {
-                cm.lo = uniform64(__hip_atomic_load(&p.pqMask[2 * slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                cm.hi = uniform64(__hip_atomic_load(&p.pqMask[2 * slotq + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                cm.lo = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                cm.hi = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                cm.inLo = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (M->ctOps > 64u)  // the second word only for trees that have such ops
+                    cm.inHi = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             }
         } else {
             m = uniform(p.pq[slotq]);
-            if (p.cull) {  // the MPU box's culling mask, made by k_precheck: in SGPRs, so every
-                           // per-primitive culling test of the walk is a scalar branch
-                cm.lo = uniform64(p.pqMask[2 * slotq]);
-                cm.hi = uniform64(p.pqMask[2 * slotq + 1]);
+            if (p.cull) {  // the MPU box's culling and op-inside masks, made by k_precheck: in
+                           // SGPRs, so every per-primitive culling test and every skip of an
+                           // op-box pruning test of the walk is a scalar branch
+                cm.lo = uniform64(p.pqMask[4 * slotq]);
+                cm.hi = uniform64(p.pqMask[4 * slotq + 1]);
+                cm.inLo = uniform64(p.pqMask[4 * slotq + 2]);
+                cm.inHi = uniform64(p.pqMask[4 * slotq + 3]);
             }
         }
         *item = m;
@@ -1605,16 +1646,19 @@ __device__ __forceinline__ void scan_counts_block(const Params& p, uint32_t b) {
 
 // Culling mask of a wave whose lanes hold points of the MPUs w (range slots): the AND of
 // those MPUs' masks (k_mpu, box grown by the normal delta), one scalar load pair per
-// distinct MPU.  A primitive culled for every one of the boxes is +0 at all the points.
+// distinct MPU.  A primitive culled for every one of the boxes is +0 at all the points; the
+// op-inside words alike: inside an op's box for every MPU's box is inside for every point.
 __device__ __forceinline__ CullMask cull_mask_mpus(const Params& p, uint32_t w) {
-    CullMask cm{~0ull, ~0ull};
+    CullMask cm{~0ull, ~0ull, ~0ull, ~0ull};
     bool todo = true;
     for (;;) {
         const uint64_t b = ballot(todo);
         if (b == 0ull) break;
         const uint32_t w0 = lane_value(w, (int)__builtin_ctzll(b));
-        cm.lo &= p.mpuMasks[2 * w0];
-        cm.hi &= p.mpuMasks[2 * w0 + 1];
+        cm.lo &= p.mpuMasks[4 * w0];
+        cm.hi &= p.mpuMasks[4 * w0 + 1];
+        cm.inLo &= p.mpuMasks[4 * w0 + 2];
+        cm.inHi &= p.mpuMasks[4 * w0 + 3];
         if (w == w0) todo = false;
     }
     return cm;

@@ -449,14 +449,14 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
     const size_t fq = 8 * front_cap(brick_count(c));
     const size_t nq = std::max<size_t>((size_t)c->pShardCap * kShards, fq);
     PSGPU_CHECK(grow(c->pq, c->capList, nq));
-    PSGPU_CHECK(grow(c->pqMask, c->capPqMask, nq * 2));
+    PSGPU_CHECK(grow(c->pqMask, c->capPqMask, nq * 4));  // culling + op-inside mask per entry
     if (fq > c->capFq) {  // ready words start at 0: no run's tag
         PSGPU_CHECK(grow(c->fqReady, c->capFq, fq));
         PSGPU_CHECK(hipMemset(c->fqReady, 0, c->capFq * sizeof(uint32_t)));
     }
     PSGPU_CHECK(grow(c->counts, c->capCounts, n));
     PSGPU_CHECK(grow(c->passed, c->capPassed, n));
-    PSGPU_CHECK(grow(c->mpuMasks, c->capMasks, 2 * n));
+    PSGPU_CHECK(grow(c->mpuMasks, c->capMasks, 4 * n));
     PSGPU_CHECK(grow(c->offs, c->capOff, n + 1));
     PSGPU_CHECK(grow(c->vk, c->capVk, (size_t)c->vShardCap * kShards));
     PSGPU_CHECK(grow(c->vp, c->capVp, (size_t)c->vShardCap * kShards));
@@ -543,6 +543,7 @@ Params make_params(psgpu_ctx* c) {
     p.counts = c->counts;
     p.passed = c->passed;
     p.bound = (c->bound && c->jit && c->model.boundable) ? 1u : 0u;
+    p.opInside = c->opInside ? 1u : 0u;
     p.mpuMasks = c->mpuMasks;
     p.offs = c->offs;
     p.vk = c->vk;
@@ -1111,6 +1112,7 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
     for (int i = 0; i <= kNumKernels; ++i) (void)hipEventCreate(&c->ev[i]);
     const char* cullEnv = getenv("PSGPU_CULL");
     if (cullEnv) c->cull = atoi(cullEnv) != 0;
+    if (const char* e = getenv("PSGPU_OP_INSIDE")) c->opInside = atoi(e) != 0;
     const char* jitEnv = getenv("PSGPU_JIT");
     if (jitEnv) c->useJit = std::min(3, std::max(0, atoi(jitEnv)));
     const char* asyncEnv = getenv("PSGPU_JIT_ASYNC");
@@ -1163,6 +1165,7 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
     if (drc != PSGPU_RET_SUCCESS) return drc;
     if (option == PSGPU_OPT_KERNEL_TIMING) c->timing = value != 0;
     else if (option == PSGPU_OPT_CULLING) c->cull = value != 0;
+    else if (option == PSGPU_OPT_OP_INSIDE) c->opInside = value != 0;
     else if (option == PSGPU_OPT_DEBUG) c->debug = (int)value;
     else if (option == PSGPU_OPT_GRAPH) c->useGraph = value != 0;
     else if (option == PSGPU_OPT_BOUND) c->bound = value != 0;
@@ -1475,6 +1478,25 @@ int psgpu_vertex_queue(psgpu_ctx* c, uint32_t* counts, uint32_t* recs, uint32_t 
             *recs++ = K.w;
             *recs++ = K.vidKey & 0xffffu;
         }
+    }
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_mpu_masks(psgpu_ctx* c, uint8_t* queued, uint64_t* masks, uint32_t capacity) {
+    if (!c || !queued || !masks) return PSGPU_RET_PARAM_ERROR;
+    int rc = psgpu_finish(c, nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    if (c->mpuCount > capacity) return PSGPU_RET_PARAM_ERROR;
+    if (c->mpuCount == 0) return PSGPU_RET_SUCCESS;
+    rc = set_device(c);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    const size_t n = c->mpuCount;
+    PSGPU_CHECK(hipMemcpy(queued, c->passed, n, hipMemcpyDeviceToHost));
+    PSGPU_CHECK(hipMemcpy(masks, c->mpuMasks, 4 * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t w = 0; w < n; ++w) {  // passed: 2 = queued for S2 (k_precheck); others have no masks
+        queued[w] = queued[w] == 2 ? 1 : 0;
+        if (!queued[w] || !c->cull)
+            for (int k = 0; k < 4; ++k) masks[4 * w + k] = 0ull;
     }
     return PSGPU_RET_SUCCESS;
 }

@@ -123,7 +123,7 @@ struct psgpu_ctx {
     // device buffers
     size_t capLb = 0, capList = 0, capCounts = 0, capOff = 0, capVk = 0, capVp = 0, capTq = 0, capV = 0, capT = 0;
     uint32_t* pq = nullptr;         // sharded S1 survivor queues
-    uint64_t* pqMask = nullptr;     // 2 words per queue entry (culling mask of the MPU box)
+    uint64_t* pqMask = nullptr;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
     size_t capPqMask = 0;
     uint32_t pShardCap = 0;
     uint32_t lastQueued = 0;        // S1 survivors queued for S2 in the last finished run
@@ -139,7 +139,8 @@ struct psgpu_ctx {
     uint8_t* passed = nullptr;      // per MPU: passed S1
     size_t capPassed = 0;
     int bound = 1;                  // prove S1 survivors empty by field bounds in k_precheck
-    uint64_t* mpuMasks = nullptr;
+    uint64_t* mpuMasks = nullptr;   // 4 words per MPU of the range (the same two masks, box + delta)
+    bool opInside = true;           // PSGPU_OPT_OP_INSIDE: k_precheck makes op-inside masks
     size_t capMasks = 0;
     uint64_t* offs = nullptr;
     VertexKey* vk = nullptr;

@@ -26,12 +26,56 @@ typedef unsigned int uint32_t;
 typedef int int32_t;
 typedef unsigned long long uint64_t;
 typedef long long int64_t;
+#elif defined(PSGPU_MODEL_NO_HIP)
+#include <stdint.h>  // a plain C++ host program (tests/cpp/op_inside_check.cpp)
 #else
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #endif
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+#define PSGPU_HD __host__ __device__
+#else
+#define PSGPU_HD
+#endif
 
 namespace psgpu {
+
+// "Op-inside" predicate (k_precheck makes one bit per op and queued MPU from it; the walks skip
+// the op-box pruning test of an op whose bit is set: Gen::emit_op, psgpu_jit.cpp).  The pruning
+// test of a point q is in(q) = OR over the axes of (q >= lo && hi >= q) (PS_Polygonizer.cpp:
+// 1228-1252), so it cannot prune anything when, along one axis, every coordinate a walk can see
+// under the MPU lies in the op's [lo, hi].  True when the MPU's extent [o, o + 7 cs] along the
+// axis, grown on both sides by m = 0.002 + 1e-5 * max(|o|, |o + 7 cs|), lies in [lo, hi] (the
+// walk's own fp32 compares; NaN compares false, and a box of magnitude >= 1e30 sets no bit).
+//
+// Why m suffices.  Write M = max(|o|, |o + 7 cs|) and u = 2^-24 (fp32 half-ulp, relative).  The
+// coordinates walked under an MPU, along one axis, are
+//   S2 corners       fl(o + fl(x cs)), x = 0..7                                  (mpu_body)
+//   edge samples     e = fl(o + fl(cs s)), s <= 7;  d = fl(fl(e + cs) - e) where the edge runs
+//                    along this axis (then s <= 6), else 0;  fl(e + fl(d t)), t in [0, 1]
+//                                                                  (edge_segment, edge_sample)
+//   roots            fl(a + fl(scale fl(b - a))), a, b two edge samples, scale in [0, 1]: k_finish
+//                    takes the MPU masks only when every vertex of the wave is on its segment
+//   normal points    fl(root + 0.001f)                                           (finish_body)
+// In exact arithmetic the first three lie in [o, o + 7 cs] and the last within 0.001f <
+// 0.0010001 of it.  Every fl() above rounds a value of magnitude <= M + 0.0011 (or a product
+// below it), so it moves the result by at most u (M + 0.0011); a coordinate depends on at most
+// 12 of them (both samples of a root counted), so it lies within 0.0010001 + 12 u (M + 0.0011)
+// < 0.00101 + 7.2e-7 M of the exact extent.  The grown box is computed with 5 roundings of its own (7 cs, o + 7 cs, 1e-5 M, m,
+// the final o - m or hi + m), each below u (M + m): it shrinks by less than 3.1e-7 (M + m), so
+// it still reaches 0.0019 + 0.9e-5 M past the exact extent, which covers the coordinates'
+// 0.00101 + 7.2e-7 M for every finite M.  No culling slack is involved.
+PSGPU_HD inline bool op_inside_axis(float opLo, float opHi, float o, float cs) {
+    const float hi = o + 7.0f * cs;
+    const float mag = __builtin_fmaxf(__builtin_fabsf(o), __builtin_fabsf(hi));
+    if (!(mag < 1e30f)) return false;
+    const float m = 0.002f + 1e-5f * mag;
+    return opLo <= o - m && hi + m <= opHi;
+}
+PSGPU_HD inline bool op_inside_box(const float opLo[3], const float opHi[3], float ox, float oy, float oz, float cs) {
+    return op_inside_axis(opLo[0], opHi[0], ox, cs) || op_inside_axis(opLo[1], opHi[1], oy, cs) ||
+           op_inside_axis(opLo[2], opHi[2], oz, cs);
+}
 
 // Node type codes of the hot path (PS_Polygonizer.h:84-91; same as PsNodeType).
 #define PSGPU_T_CYLINDER 0
@@ -214,7 +258,8 @@ struct Params {
     uint32_t brickStride;   // wave W takes brick (W * brickStride) mod bricks (coprime: a
                             // permutation that spreads the surface's heavy bricks over the CUs)
     uint32_t* pq;           // kShards queues of pShardCap S1 survivors (global MPU ids)
-    uint64_t* pqMask;       // per queue entry: the MPU box's culling mask (2 words, by k_precheck)
+    uint64_t* pqMask;       // per queue entry: the MPU box's culling mask (2 words) and its op-inside
+                            // mask (2 words, op_inside_box), by k_precheck
     uint32_t pShardCap;     // 8 * ceil(precheck waves / kShards): cannot overflow
     uint32_t* fqReady;      // k_front: per queue entry, the run's tag once the entry is published
     uint32_t fqCap;         // k_front: entries per sub-queue (8 sub-queues at pq + k * fqCap)
@@ -222,7 +267,9 @@ struct Params {
     uint64_t* counts;       // mpuCount: V | T << 32 per MPU of the range (0 if S1 failed)
     uint8_t* passed;        // mpuCount: 1 if the MPU passed S1 (PsMpuStats::passedPrecheck)
     uint32_t bound;         // k_precheck proves S1 survivors empty by field bounds
-    uint64_t* mpuMasks;     // 2 * mpuCount: culling mask of each queued MPU's box + delta (k_precheck)
+    uint32_t opInside;      // k_precheck makes op-inside masks (0: zero masks, every pruning test runs)
+    uint64_t* mpuMasks;     // 4 * mpuCount: culling mask of each queued MPU's box + delta, then its
+                            // op-inside mask (k_precheck)
     uint64_t* offs;         // mpuCount + 1: exclusive scan of counts
     uint64_t* scanStatus;   // offsets-scan look-back words of this run (zeroed by the previous run)
     uint64_t* scanStatusNext;

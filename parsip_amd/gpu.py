@@ -76,7 +76,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
-    "psgpu_vertex_queue",
+    "psgpu_vertex_queue", "psgpu_mpu_masks",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -99,6 +99,7 @@ OPT_TIER_RUNS = 18
 OPT_MPU_TICKS = 19
 OPT_FUSED_SURFACE = 21
 OPT_FRONT = 22
+OPT_OP_INSIDE = 23
 LAUNCH_TREE_SPLIT, LAUNCH_SURFACE, LAUNCH_FRONT, LAUNCH_RERUN = 1, 2, 4, 8  # PsMeshInfo.launchFlags
 DEBUG_SURFACE_LATE_SCAN = 1 << 25  # test hooks of the in-kernel waits (OPT_DEBUG bits, one run each)
 DEBUG_LOOKBACK_TIMEOUT = 1 << 26
@@ -187,6 +188,7 @@ def load(build_if_missing: bool = True):
         "psgpu_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
         "psgpu_weld_times": ([vp, vp, i32, vp], i32),
         "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
+        "psgpu_mpu_masks": ([vp, vp, vp, u32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -420,6 +422,18 @@ class Polygonizer:
                "psgpu_vertex_queue")
         ends = np.cumsum(counts.astype(np.int64))
         return counts, [recs[e - n:e] for e, n in zip(ends, counts.astype(np.int64))]
+
+    def mpu_masks(self) -> tuple[np.ndarray, np.ndarray]:
+        """Debug export of the finished run's per-MPU masks: queued (bool per MPU of the range:
+        k_precheck queued it for S2) and an (n, 4) uint64 array, per MPU its culling mask (words
+        0-1, bit i: primitive i) and its op-inside mask (words 2-3, bit k: op k); zeros for MPUs
+        that were not queued."""
+        info = self.finish()
+        queued = np.zeros(max(info.ctMPUs, 1), np.uint8)
+        masks = np.zeros((max(info.ctMPUs, 1), 4), np.uint64)
+        _check(self._L.psgpu_mpu_masks(self._ctx, queued.ctypes.data, masks.ctypes.data, len(queued)),
+               "psgpu_mpu_masks")
+        return queued[:info.ctMPUs].astype(bool), masks[:info.ctMPUs]
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info = self.finish()
