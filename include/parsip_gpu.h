@@ -270,8 +270,9 @@ typedef struct PsWeldDevice {    /* valid until the next psgpu_weld / psgpu_dest
 } PsWeldDevice;
 /* Weld the context's finished run on the context's stream; blocking.  PSGPU_RET_PARAM_ERROR
  * when there is no finished run: none yet, or a psgpu_set_model / psgpu_polygonize since the
- * last psgpu_finish; and when the run reported an overflow MPU (its records are cut) or a
- * lattice axis has 2^20 / 7 MPUs or more.  An empty mesh welds to an empty mesh. */
+ * last psgpu_finish; and when the run reported an overflow MPU (the run exceeds the reference's
+ * 512 vertices / triangles per MPU and is refused; its records are complete, nothing cuts
+ * them) or a lattice axis has 2^20 / 7 MPUs or more.  An empty mesh welds to an empty mesh. */
 int  psgpu_weld(psgpu_ctx* ctx, PsWeldInfo* info);
 /* The welded mesh in HBM / on the host (any pointer may be NULL): PSGPU_RET_PARAM_ERROR
  * before a successful psgpu_weld of the current run. */

@@ -312,7 +312,7 @@ extern "C" {
 
 int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
     if (!weld_run_ready(c)) return PSGPU_RET_PARAM_ERROR;
-    if (c->info.firstOverflowMPU >= 0) return PSGPU_RET_PARAM_ERROR;  // an MPU's records were cut at 512
+    if (c->info.firstOverflowMPU >= 0) return PSGPU_RET_PARAM_ERROR;  // past the reference's 512 per MPU (records complete)
     for (int a = 0; a < 3; ++a)
         if (7ull * c->dims[a] >= (1ull << kCoordBits)) return PSGPU_RET_PARAM_ERROR;
     int rc = set_device(c);

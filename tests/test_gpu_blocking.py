@@ -185,6 +185,7 @@ def test_blocking_export_fuzz_sequence(oracle):
     import test_gpu_fuzz as fz
 
     p = gpu.Polygonizer(0)
+    overflowed = []  # seeds that take the overflow branch (tests/test_gpu_dense.py asserts that contract)
     try:
         p.set_option(gpu.OPT_DEBUG, gpu.DEBUG_EXPORT_POISON | gpu.DEBUG_EXPORT_STRAGGLER)
         for seed in range(0, 40, 3):
@@ -196,9 +197,11 @@ def test_blocking_export_fuzz_sequence(oracle):
             om = oracle.polygonize(model, cs, 0, 0xFFFFFFFF, threads=8)
             if rc == soa.RET_MPU_VT_OVERFLOW:  # an MPU past the reference's 512 V / T
                 assert (om.stats[:, 2:4] > 512).any(), seed
+                overflowed.append(seed)
                 continue
             assert rc == soa.RET_SUCCESS and ct == n, (seed, rc, ct)
             want = mesh_digests(om.stats[:, :4], om.pos, om.nrm, om.col, om.tris)
             assert polympus_digests(mpus, stats) == want, seed
+        print(f"fuzz sequence: {len(overflowed)} of {len(range(0, 40, 3))} seeds returned MPU_VT_OVERFLOW: {overflowed}")
     finally:
         p.close()
