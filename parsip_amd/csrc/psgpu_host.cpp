@@ -434,9 +434,7 @@ size_t brick_count(const psgpu_ctx* c) {
     return (size_t)bd[0] * bd[1] * bd[2];
 }
 
-// k_front sub-queue capacity for a k_precheck grid of `blocks` blocks of `mpb` bricks: every
-// 8th block's bricks x 8 MPUs; front_cap(bricks) bounds it for both grids (2 and 4 bricks per block)
-uint32_t front_sub_cap(uint32_t blocks, uint32_t mpb) { return 8u * mpb * ((blocks + 7u) / 8u); }
+// front_sub_cap (psgpu_plan.h) for both k_precheck grids (2 and 4 bricks per block)
 uint32_t front_cap(size_t bricks) {
     const uint32_t b = (uint32_t)bricks;
     return std::max(front_sub_cap((b + 1u) / 2u, 2u), front_sub_cap((b + 3u) / 4u, 4u));
@@ -470,31 +468,33 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
     return PSGPU_RET_SUCCESS;
 }
 
-// k_precheck / k_mpu with the walk split at the root (two waves per brick / MPU)
-// (2: when the last finished run of this range queued at most splitMaxQueued MPUs for S2 --
-// a launch too small to fill the device, whose span is its heaviest items' walks)
-bool use_split(const psgpu_ctx* c) {
-    if (!c->jit || !c->jit->precheckS || !c->splittable) return false;
-    return c->treeSplit == 1 || (c->treeSplit == 2 && c->haveQueued && c->lastQueued <= c->splitMaxQueued);
+// The launch shape of the context's next run (psgpu_plan.h decides it, from these inputs alone).
+// separate: finish re-runs a run whose in-kernel wait gave up, as separate launches.
+LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
+    PlanInput in{};
+    in.numCUs = c->numCUs;
+    in.bricks = brick_count(c);
+    in.mpuCount = c->mpuCount;
+    in.opt = c->opt;
+    in.last = c->last;
+    in.alone = c->alone;
+    in.crowded = c->crowded;
+    in.mpuTicks = c->mpuTicksOpt != 0;
+    in.splittable = c->splittable;
+    if (const JitKernels* J = c->jit.get()) {
+        in.jit = true;
+        in.hasPrecheckS = J->precheckS != nullptr;
+        in.hasSurface = J->surface != nullptr;
+        in.hasSurfaceW = J->surfaceW != nullptr;
+        in.hasFront = J->front != nullptr;
+        in.hasFrontS = J->frontS != nullptr;
+    }
+    in.separate = separate;
+    in.shortGrid = (c->debug & (1 << 20)) != 0;
+    return plan_launch(in);
 }
 
-// k_precheck + k_mpu as one launch (k_front) for the next run: 1 forces it, 2 (default) when
-// the k_precheck grid is at most 8 blocks per CU -- C3 and its rank shares, whose step the
-// boundary and the S1 tail weigh on (the driver's C3 window -7 %, one engine -2.4 %), not C5's
-// 512^3 frame (13 k S1 blocks: +4.6 %, the fused kernel's registers cost its S1 waves a slot;
-// profiles/r06_front_ab.txt).  Never with per-MPU ticks (MPUSTATS: S1 and S2 would write an
-// MPU's tick words from two XCDs in one launch), on a crowded device, or while finish re-runs a
-// run whose in-kernel wait gave up (surfaceOff).
-bool use_front(const psgpu_ctx* c) {
-    if (!c->jit || c->front == 0 || c->surfaceOff || c->crowded || c->mpuTicksOpt) return false;
-    const bool split = use_split(c);
-    if (!(split ? c->jit->frontS : c->jit->front)) return false;
-    if (c->front == 1) return true;
-    const size_t mpb = split ? 2u : (size_t)kMpusPerBlock;
-    return (brick_count(c) + mpb - 1) / mpb <= 8u * (size_t)c->numCUs;
-}
-
-Params make_params(psgpu_ctx* c) {
+Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
     Params p;
     memset(&p, 0, sizeof(p));  // padding too: graph replay compares parameter bytes
     p.model = c->dModel;
@@ -511,33 +511,16 @@ Params make_params(psgpu_ctx* c) {
     p.mpuCount = c->mpuCount;
     p.cull = (uint32_t)c->cull;
     brick_layout(c, &p.brickI0, p.brickDims);
-    const bool split = use_split(c);
-    const uint32_t mpb = split ? 2u : (uint32_t)kMpusPerBlock;  // MPUs (bricks) per block
-    p.preBlocks = (uint32_t)((brick_count(c) + mpb - 1) / mpb);
+    p.preBlocks = plan.preBlocks;
     p.brickStride = brick_stride((uint32_t)brick_count(c), (c->debug & 16384) != 0);
     p.pq = c->pq;
     p.pqMask = c->pqMask;
     p.pShardCap = c->pShardCap;
-    // k_mpu: one wave per queued survivor, as many as the last finished run queued + 1/4
-    // (a run that queues more is re-run by finish(): the grid then fits exactly)
-    const uint32_t maxBlocks = (c->mpuCount + mpb - 1) / mpb;
-    const uint32_t margin = c->lastQueued / c->mpuMarginDiv + (c->mpuMarginDiv > 4 ? 64u : 256u);
-    const uint32_t want = c->haveQueued ? (c->lastQueued + margin + mpb - 1) / mpb : maxBlocks;
-    p.mpuBlocks = std::max(1u, std::min(maxBlocks, want));
+    p.mpuBlocks = plan.mpuBlocks;
     p.fqReady = c->fqReady;
-    p.fqCap = front_sub_cap(p.preBlocks, mpb);
-    if (use_front(c)) {
-        // k_front's S2 blocks: 8 per row, a row takes mpb entries of each sub-queue; rows for the
-        // last run's largest sub-queue + 1/4 (or every entry of a sub-queue without a last run)
-        const uint32_t sub = !c->haveQueued ? p.fqCap
-                             : (c->lastSubMax ? c->lastSubMax : (c->lastQueued + 7u) / 8u) + c->lastQueued / 32u + 32u;
-        const uint32_t rows = (std::min(sub, p.fqCap) + mpb - 1u) / mpb;
-        p.mpuBlocks = 8u * std::max(1u, rows);
-    }
-    if (c->debug & (1 << 20)) p.mpuBlocks = use_front(c) ? 8u : 1u;  // test hook: a k_mpu grid that falls short (finish re-runs)
-    p.scanChunks = (c->mpuCount + kScanItems * kScanMaxBlocks - 1) / (kScanItems * kScanMaxBlocks);
-    if (p.scanChunks == 0) p.scanChunks = 1;
-    p.scanBlocks = (c->mpuCount + kScanItems * p.scanChunks - 1) / (kScanItems * p.scanChunks);
+    p.fqCap = plan.fqCap;
+    p.scanChunks = plan.scanChunks;
+    p.scanBlocks = plan.scanBlocks;
     p.scanStatus = c->scanStatus + (size_t)c->parity * kScanMaxBlocks;
     p.scanStatusNext = c->scanStatus + (size_t)(c->parity ^ 1u) * kScanMaxBlocks;
     p.counts = c->counts;
@@ -576,108 +559,44 @@ hipError_t launch_jit(hipFunction_t f, uint32_t blocks, uint32_t threads, size_t
     return hipModuleLaunchKernel(f, blocks, 1, 1, threads, 1, 1, (unsigned)lds, s, args, nullptr);
 }
 
-// One polygonization = 5 kernels, no copies or fills: k_precheck resets the counters,
-// k_finish publishes them to mapped host memory.
-// The five launches of one polygonization (shared by direct launch and graph capture).
-// k_finish layout for the next run (vertices per wave): a quad of lanes per vertex (16) when
-// the last run's vertices, 16 per wave, fit the persistent grid's waves in one pass (each
-// wave then walks a quarter of what a 64-vertex wave does), else a pair of lanes (32) when
-// they do 32 per wave, otherwise one lane per vertex (64: fewest waves in total).
-// A run alone on its device (c->alone) takes at most 32 per wave: the spans, not the total
-// work, set its time (C3 full grid, one engine: 0.1077 vs 0.1110 ms with the quad k_vertex).
-int finish_vpw(const psgpu_ctx* c) {
-    if (c->finishQuad == 0) return 64;
-    if (c->finishQuad == 1) return 16;
-    if (c->finishQuad == 3) return 32;
-    const uint64_t waves = (uint64_t)c->numCUs * (uint64_t)c->finishBlocksPerCU * 4u;
-    if (c->lastV == 0) return 64;
-    if ((uint64_t)c->lastV <= 16u * waves) return 16;
-    if ((uint64_t)c->lastV <= 32u * waves || c->alone) return 32;
-    return 64;
-}
-
-// k_vertex layout for the next run (vertices per wave): one lane per vertex (64: each lane's
-// 4 edge samples as one walk, the least total work) when the last run's vertices, 16 per
-// wave, would take more than one pass of the persistent grid; otherwise a quad of lanes per
-// vertex (16: a quarter of the walk per wave, shorter spans).  The interpreter has the quad
-// layout only.
-int vertex_vpw(const psgpu_ctx* c) {
-    if (!c->jit || c->vertexWide == 0) return 16;
-    if (c->vertexWide == 1) return 64;
-    const uint64_t waves = (uint64_t)c->numCUs * (uint64_t)c->vertexBlocksPerCU * 4u;
-    return (uint64_t)c->lastV > 16u * waves && !c->alone ? 64 : 16;  // a lone run: the quad
-}
-
-// k_vertex + k_finish as one launch (k_surface) for the next run: 1 forces it, 2 (default) when
-// both would take their quad layouts (a launch too small to fill the device: its step is the
-// launch floor); only with the small-launch kernels (compiled with the split)
-bool use_surface(const psgpu_ctx* c) {
-    if (!c->jit || !c->jit->surface || c->fusedSurface == 0 || c->surfaceOff || c->crowded) return false;
-    if (c->fusedSurface == 3) return c->jit->surfaceW != nullptr;  // the wide variant, every launch
-    // a run alone on the device (a blocking caller, a frame-at-a-time editor) is bound by its
-    // spans: the quad layouts in one launch, while their waves fill the device at most ~8 times
-    // (C3 alone 0.110 vs 0.115 ms; C5's 512^3 frame, far more vertices, 0.613 vs 0.600:
-    // profiles/r06_latency_ab.txt)
-    const uint64_t loneMaxV = 16ull * 8ull * 24ull * (uint64_t)c->numCUs;  // 16 a wave, 24 waves a CU, 8 passes
-    return c->fusedSurface == 1 ||
-           (c->lastV != 0 && ((c->alone && c->lastV <= loneMaxV) || (vertex_vpw(c) == 16 && finish_vpw(c) == 16)));
-}
-
-int launch_all(psgpu_ctx* c, const Params& pin, hipStream_t s, bool timed) {
+// The launches of one polygonization as the plan shapes them (shared by direct launch and
+// graph capture): k_precheck and k_mpu, or both as k_front, then k_vertex and k_finish, or both
+// as k_surface.  No copies or fills.
+int launch_all(psgpu_ctx* c, const Params& pin, const LaunchPlan& plan, hipStream_t s, bool timed) {
     Params p = pin;
-    const uint32_t persistV = (uint32_t)(c->numCUs * c->vertexBlocksPerCU);
-    const uint32_t persistF = (uint32_t)(c->numCUs * c->finishBlocksPerCU);
-    const int vpw = finish_vpw(c);
     JitKernels* J = c->jit.get();
+    // the split kernel's blocks hold 2 MPUs, the others 4 (mpu_lds_bytes(0): 4 MPUs' LDS)
+    const size_t mpuLds = mpu_lds_bytes(0) / (plan.split ? 2 : 1);
     if (timed) PSGPU_CHECK(hipEventRecord(c->ev[0], s));
-    const bool split = use_split(c);
-    if (use_front(c)) {  // S1 blocks, then S2 blocks taking the survivors as they are published
-        PSGPU_CHECK(launch_jit(split ? J->frontS : J->front, p.preBlocks + p.mpuBlocks, 256,
-                               mpu_lds_bytes(0) / (split ? 2 : 1), s, p));
+    if (plan.front) {  // S1 blocks, then S2 blocks taking the survivors as they are published
+        PSGPU_CHECK(launch_jit(plan.split ? J->frontS : J->front, plan.preBlocks + plan.mpuBlocks, 256, mpuLds, s, p));
         if (timed) {
             PSGPU_CHECK(hipEventRecord(c->ev[1], s));
             PSGPU_CHECK(hipEventRecord(c->ev[2], s));
         }
     } else {
-    if (J) PSGPU_CHECK(launch_jit(split ? J->precheckS : J->precheck, p.preBlocks, 256, 0, s, p));
-    else PSGPU_CHECK(launch_precheck(p, s));
-    if (timed) PSGPU_CHECK(hipEventRecord(c->ev[1], s));
-    // the split kernel's blocks hold 2 MPUs, the others 4 (mpu_lds_bytes(0): 4 MPUs' LDS)
-    if (J) PSGPU_CHECK(launch_jit(split ? J->mpuS : J->mpu, p.mpuBlocks, 256, mpu_lds_bytes(0) / (split ? 2 : 1), s, p));
-    else PSGPU_CHECK(launch_mpu(p, s));
-    if (timed) PSGPU_CHECK(hipEventRecord(c->ev[2], s));
+        if (J) PSGPU_CHECK(launch_jit(plan.split ? J->precheckS : J->precheck, plan.preBlocks, 256, 0, s, p));
+        else PSGPU_CHECK(launch_precheck(p, s));
+        if (timed) PSGPU_CHECK(hipEventRecord(c->ev[1], s));
+        if (J) PSGPU_CHECK(launch_jit(plan.split ? J->mpuS : J->mpu, plan.mpuBlocks, 256, mpuLds, s, p));
+        else PSGPU_CHECK(launch_mpu(p, s));
+        if (timed) PSGPU_CHECK(hipEventRecord(c->ev[2], s));
     }
-    // k_vertex's first scanBlocks blocks also compute the mesh offsets (all co-resident)
-    const int vpwV = J ? vertex_vpw(c) : 16;
-    uint32_t gridV = std::max(persistV, p.scanBlocks);
-    uint32_t gridF = persistF;
-    if (c->gridFit && c->lastV) {
-        // grids fitted to the last finished run: a wave per batch of its vertices + 1/8 (both
-        // kernels stride over any rest), not the persistent grids' mostly empty waves
-        const uint64_t vv = (uint64_t)c->lastV + c->lastV / 8 + 256;
-        gridV = std::max(p.scanBlocks, std::min<uint32_t>(gridV, (uint32_t)((vv + 4ull * vpwV - 1) / (4ull * vpwV))));
-        gridF = std::min<uint32_t>(gridF, (uint32_t)((vv + 4ull * vpw - 1) / (4ull * vpw)));
-    }
-    if (use_surface(c)) {  // both quad layouts in one launch: the vertex grid (16 per wave)
-        const bool wide = c->fusedSurface == 3;  // or one lane per vertex: k_finish's grid (64 per wave)
-        const uint32_t perBlock = wide ? 256u : 64u;
-        uint32_t gridS = std::max(wide ? persistF : persistV, p.scanBlocks);
-        if (c->gridFit && c->lastV) {
-            const uint64_t vv = (uint64_t)c->lastV + c->lastV / 8 + 256;
-            gridS = std::max(p.scanBlocks, std::min<uint32_t>(gridS, (uint32_t)((vv + perBlock - 1) / perBlock)));
-        }
-        PSGPU_CHECK(launch_jit(wide ? J->surfaceW : J->surface, gridS, 256, 0, s, p));
+    // k_vertex's (k_surface's) first scanBlocks blocks also compute the mesh offsets
+    if (plan.surface) {
+        PSGPU_CHECK(launch_jit(plan.surfaceWide ? J->surfaceW : J->surface, plan.gridSurface, 256, 0, s, p));
         if (timed) {
             PSGPU_CHECK(hipEventRecord(c->ev[3], s));
             PSGPU_CHECK(hipEventRecord(c->ev[4], s));
         }
         return PSGPU_RET_SUCCESS;
     }
-    if (J) PSGPU_CHECK(launch_jit(vpwV == 64 ? J->vertexW : J->vertex, gridV, 256, 0, s, p));
-    else PSGPU_CHECK(launch_vertex(p, s, gridV));
+    if (J) PSGPU_CHECK(launch_jit(plan.vpwVertex == 64 ? J->vertexW : J->vertex, plan.gridVertex, 256, 0, s, p));
+    else PSGPU_CHECK(launch_vertex(p, s, plan.gridVertex));
     if (timed) PSGPU_CHECK(hipEventRecord(c->ev[3], s));
-    if (J) PSGPU_CHECK(launch_jit(vpw == 16 ? J->finishQ : (vpw == 32 ? J->finishP : J->finish), gridF, 256, 0, s, p));
-    else PSGPU_CHECK(launch_finish(p, s, gridF, vpw));
+    const uint32_t vpw = plan.vpwFinish;
+    if (J) PSGPU_CHECK(launch_jit(vpw == 16 ? J->finishQ : (vpw == 32 ? J->finishP : J->finish), plan.gridFinish, 256, 0, s, p));
+    else PSGPU_CHECK(launch_finish(p, s, plan.gridFinish, (int)vpw));
     if (timed) PSGPU_CHECK(hipEventRecord(c->ev[4], s));
     return PSGPU_RET_SUCCESS;
 }
@@ -689,12 +608,13 @@ void drop_graphs(psgpu_ctx* c) {
     }
 }
 
-// One polygonization = 5 kernels, no copies or fills: k_precheck needs nothing reset
-// (k_finish of the previous run reset this run's counters) and k_finish publishes the
-// counters to mapped host memory.  Replayed from a hipGraph (one per counter set) while
-// the launch parameters repeat, e.g. per frame of an animation.
+// Enqueue one polygonization: its shape is planned once, here, and kept as c->run.  k_precheck
+// needs nothing reset (k_finish of the previous run reset this run's counters) and k_finish
+// publishes the counters to mapped host memory.  Replayed from a hipGraph (one per counter
+// set) while the kernels, the parameters and the plan repeat, e.g. per frame of an animation.
+// separate: a protocol-error re-run, as separate launches.
 void reset_run_state(psgpu_ctx* c);
-int enqueue(psgpu_ctx* c, hipStream_t s) {
+int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
     if (c->mpuCount == 0) {  // nothing to launch: an empty result
         c->runTicks = c->mpuTicksOpt != 0;
         memset(c->hostCtr, 0, sizeof(DevCounters));
@@ -718,36 +638,29 @@ int enqueue(psgpu_ctx* c, hipStream_t s) {
     // drain once in 2^32 runs)
     if (c->epochRuns >= 0xffffffffull) reset_run_state(c);
     ++c->epochRuns;
-    const Params p = make_params(c);
+    const LaunchPlan plan = c->run = plan_run(c, separate);
+    const Params p = make_params(c, plan);
     c->runTicks = p.mpuTicks != nullptr;
     c->debug &= ~((1 << 20) | (1 << 25) | (1 << 26) | (1 << 27));  // the short-grid / protocol test hooks apply to one run
     if (p.spans) c->spanNext++;
-    c->runMpuBlocks = p.mpuBlocks;
-    c->runMpb = use_split(c) ? 2u : (uint32_t)kMpusPerBlock;
     const uint32_t slot = c->parity;
     c->parity ^= 1u;  // k_finish of this run resets the other set for the next run
     const bool timed = c->timing != 0;
-    c->runSurface = use_surface(c);
-    c->runFront = use_front(c);
-    c->runSplit = use_split(c);
     if (c->stamps)  // waves that do not run leave no stale records
         PSGPU_CHECK(hipMemsetAsync(c->stamps, 0, (size_t)kNumStampKernels * c->stampCap * 24 + (size_t)c->stampCap * 64, s));
     if (!c->useGraph || timed || s == nullptr) {
-        const int rc = launch_all(c, p, s, timed);
+        const int rc = launch_all(c, p, plan, s, timed);
         if (rc != PSGPU_RET_SUCCESS) reset_run_state(c);
         return rc;
     }
     psgpu_ctx::GraphSlot& g = c->graphs[slot];
-    const uint32_t shape[6] = {(uint32_t)c->vertexBlocksPerCU, (uint32_t)c->finishBlocksPerCU, (uint32_t)c->numCUs,
-                               (uint32_t)finish_vpw(c), (uint32_t)vertex_vpw(c),
-                               (use_split(c) ? 1u : 0u) | (use_surface(c) ? 2u : 0u) | (use_front(c) ? 4u : 0u)};
     if (!(g.exec && g.jit == c->jit.get() && memcmp(&g.key, &p, sizeof(Params)) == 0 &&
-          memcmp(g.shape, shape, sizeof(shape)) == 0)) {
+          memcmp(&g.plan, &plan, sizeof(LaunchPlan)) == 0)) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         g = psgpu_ctx::GraphSlot{};
         hipGraph_t graph = nullptr;
         PSGPU_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = launch_all(c, p, s, false);
+        const int rc = launch_all(c, p, plan, s, false);
         const hipError_t ec = hipStreamEndCapture(s, &graph);
         if (rc != PSGPU_RET_SUCCESS) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -760,7 +673,7 @@ int enqueue(psgpu_ctx* c, hipStream_t s) {
         PSGPU_CHECK(ei);
         g.key = p;
         g.jit = c->jit.get();
-        memcpy(g.shape, shape, sizeof(shape));
+        g.plan = plan;
     }
     PSGPU_CHECK(hipGraphLaunch(g.exec, s));
     return PSGPU_RET_SUCCESS;
@@ -815,7 +728,7 @@ void jit_poll(psgpu_ctx* c, bool wait) {
     c->jit = jit_load(*code, c->device, &c->jitError);
     if (!c->jit && code->code.size() && c->jitError.find("dropped") != std::string::npos) {
         // the cached object would not load: compile it afresh (bypassing the disk cache)
-        c->jitFut = jit_request(c->model, c->useJit == 2, false, c->treeSplit != 0);
+        c->jitFut = jit_request(c->model, c->useJit == 2, false, c->opt.treeSplit != 0);
         c->jitPending = true;
         if (wait) jit_poll(c, true);
         return;
@@ -850,7 +763,7 @@ void tier_poll(psgpu_ctx* c, bool wait) {
 void tier_count(psgpu_ctx* c) {
     if (c->useJit != 3 || c->tier != 1 || c->tier2Pending || c->tier2Failed) return;
     if (++c->staticRuns < c->tierRuns) return;
-    c->tier2Fut = jit_request(c->model, true, true, c->treeSplit != 0);
+    c->tier2Fut = jit_request(c->model, true, true, c->opt.treeSplit != 0);
     c->tier2Pending = true;
 }
 
@@ -879,7 +792,7 @@ void jit_start(psgpu_ctx* c) {
         }
     }
     if (!c->useJit || !c->haveModel) return;
-    c->jitFut = jit_request(c->model, c->useJit == 2, true, c->treeSplit != 0);
+    c->jitFut = jit_request(c->model, c->useJit == 2, true, c->opt.treeSplit != 0);
     c->jitPending = true;
     jit_poll(c, !c->jitAsync);
 }
@@ -1069,7 +982,7 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, deviceOrdinal) == hipSuccess && prop.multiProcessorCount > 0)
         c->numCUs = prop.multiProcessorCount;
-    c->splitMaxQueued = 4u * (uint32_t)c->numCUs;
+    c->opt.splitMaxQueued = 4u * (uint32_t)c->numCUs;
     const CubeTables& T = cube_tables();
     CubeTablesDev tabHost{};
     fill_device_tables(T, tabHost);
@@ -1117,12 +1030,12 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
     if (jitEnv) c->useJit = std::min(3, std::max(0, atoi(jitEnv)));
     const char* asyncEnv = getenv("PSGPU_JIT_ASYNC");
     if (asyncEnv) c->jitAsync = atoi(asyncEnv) != 0;
-    if (const char* e = getenv("PSGPU_GRID_FIT")) c->gridFit = atoi(e) != 0;          // 0: persistent grids
-    if (const char* e = getenv("PSGPU_FINISH_QUAD")) c->finishQuad = std::min(3, std::max(0, atoi(e)));
-    if (const char* e = getenv("PSGPU_VERTEX_WIDE")) c->vertexWide = std::min(2, std::max(0, atoi(e)));
-    if (const char* e = getenv("PSGPU_MPU_MARGIN")) c->mpuMarginDiv = std::max(1, atoi(e));
-    if (const char* e = getenv("PSGPU_FUSED_SURFACE")) c->fusedSurface = std::min(3, std::max(0, atoi(e)));
-    if (const char* e = getenv("PSGPU_FRONT")) c->front = std::min(2, std::max(0, atoi(e)));
+    if (const char* e = getenv("PSGPU_GRID_FIT")) c->opt.gridFit = atoi(e) != 0;          // 0: persistent grids
+    if (const char* e = getenv("PSGPU_FINISH_QUAD")) c->opt.finishQuad = std::min(3, std::max(0, atoi(e)));
+    if (const char* e = getenv("PSGPU_VERTEX_WIDE")) c->opt.vertexWide = std::min(2, std::max(0, atoi(e)));
+    if (const char* e = getenv("PSGPU_MPU_MARGIN")) c->opt.mpuMarginDiv = std::max(1, atoi(e));
+    if (const char* e = getenv("PSGPU_FUSED_SURFACE")) c->opt.fusedSurface = std::min(3, std::max(0, atoi(e)));
+    if (const char* e = getenv("PSGPU_FRONT")) c->opt.front = std::min(2, std::max(0, atoi(e)));
     *out = c;
     return PSGPU_RET_SUCCESS;
 }
@@ -1187,23 +1100,23 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
         c->haveResult = false;
         ++c->runSeq;
     }
-    else if (option == PSGPU_OPT_VERTEX_BLOCKS_PER_CU && value >= 1 && value <= 32) c->vertexBlocksPerCU = (int)value;
-    else if (option == PSGPU_OPT_FINISH_BLOCKS_PER_CU && value >= 1 && value <= 32) c->finishBlocksPerCU = (int)value;
-    else if (option == PSGPU_OPT_FINISH_QUAD && value >= 0 && value <= 3) c->finishQuad = (int)value;
-    else if (option == PSGPU_OPT_VERTEX_WIDE && value >= 0 && value <= 2) c->vertexWide = (int)value;
+    else if (option == PSGPU_OPT_VERTEX_BLOCKS_PER_CU && value >= 1 && value <= 32) c->opt.vertexBlocksPerCU = (int)value;
+    else if (option == PSGPU_OPT_FINISH_BLOCKS_PER_CU && value >= 1 && value <= 32) c->opt.finishBlocksPerCU = (int)value;
+    else if (option == PSGPU_OPT_FINISH_QUAD && value >= 0 && value <= 3) c->opt.finishQuad = (int)value;
+    else if (option == PSGPU_OPT_VERTEX_WIDE && value >= 0 && value <= 2) c->opt.vertexWide = (int)value;
     else if (option == PSGPU_OPT_TREE_SPLIT && value >= 0 && value <= 2) {
-        const bool recompile = value != 0 && c->treeSplit == 0 && c->haveModel && c->splittable &&
+        const bool recompile = value != 0 && c->opt.treeSplit == 0 && c->haveModel && c->splittable &&
                                !(c->jit && c->jit->precheckS);
-        c->treeSplit = (int)value;
+        c->opt.treeSplit = (int)value;
         if (recompile) {  // the loaded kernels lack the split variants: generate them
             if (c->pending) (void)hipStreamSynchronize(c->runStream);
             drop_graphs(c);
             jit_start(c);
         }
     }
-    else if (option == PSGPU_OPT_SPLIT_MAX_QUEUED && value >= 0 && value <= 0xffffffffll) c->splitMaxQueued = (uint32_t)value;
-    else if (option == PSGPU_OPT_FUSED_SURFACE && value >= 0 && value <= 3) c->fusedSurface = (int)value;
-    else if (option == PSGPU_OPT_FRONT && value >= 0 && value <= 2) c->front = (int)value;
+    else if (option == PSGPU_OPT_SPLIT_MAX_QUEUED && value >= 0 && value <= 0xffffffffll) c->opt.splitMaxQueued = (uint32_t)value;
+    else if (option == PSGPU_OPT_FUSED_SURFACE && value >= 0 && value <= 3) c->opt.fusedSurface = (int)value;
+    else if (option == PSGPU_OPT_FRONT && value >= 0 && value <= 2) c->opt.front = (int)value;
     else if (option == PSGPU_OPT_TIER_RUNS && value >= 1 && value <= (1 << 30)) c->tierRuns = (int)value;
     else if (option == PSGPU_OPT_JIT) {
         if (value < 0 || value > 3) return PSGPU_RET_PARAM_ERROR;
@@ -1300,8 +1213,8 @@ int psgpu_polygonize(psgpu_ctx* c, float cellsize, uint32_t mpuBegin, uint32_t m
         // one -- size k_mpu for the whole range (no re-run) until a run of it finishes.  A new
         // model on the same lattice (an animation frame) keeps the prediction; a frame that
         // queues more is re-run by finish(), and psgpu_comm_result agrees on that collectively.
-        c->haveQueued = false;
-        c->lastV = 0;
+        c->last.haveQueued = false;
+        c->last.lastV = 0;
     }
     c->lastCs = cellsize;
     c->mpuBegin = begin;
@@ -1356,18 +1269,18 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
                 mv = std::max(mv, h.shard[k].v);
                 mt = std::max(mt, h.shard[k].t);
             }
-            bool gridShort = c->mpuCount > 0 && Q > c->runMpb * c->runMpuBlocks;
-            if (c->runFront) {  // k_front: each sub-queue against its own rows of S2 blocks
+            bool gridShort = c->mpuCount > 0 && Q > c->run.mpb * c->run.mpuBlocks;
+            if (c->run.front) {  // k_front: each sub-queue against its own rows of S2 blocks
                 uint32_t sub = 0;
                 for (int k = 0; k < 8; ++k) sub = std::max(sub, h.shard[k].p);
-                gridShort = c->mpuCount > 0 && sub > c->runMpb * (c->runMpuBlocks / 8u);
-                c->lastSubMax = sub;
+                gridShort = c->mpuCount > 0 && sub > c->run.mpb * (c->run.mpuBlocks / 8u);
+                c->last.lastSubMax = sub;
             } else {
-                c->lastSubMax = 0;
+                c->last.lastSubMax = 0;
             }
-            c->lastQueued = Q;
-            c->lastV = V;
-            c->haveQueued = c->mpuCount > 0;
+            c->last.lastQueued = Q;
+            c->last.lastV = V;
+            c->last.haveQueued = c->mpuCount > 0;
             c->seenV = std::max(c->seenV, V);
             c->seenT = std::max(c->seenT, T);
             c->seenShardV = std::max(c->seenShardV, mv);
@@ -1397,11 +1310,9 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
             // scan): the run's offsets are not trusted.  Re-run it once as k_vertex + k_finish,
             // the chain whose kernel boundaries order the scan; a second error fails the call.
             fprintf(stderr, "psgpu: device protocol error 0x%x (%s): re-running as separate launches\n",
-                    h.error | h.surfaceErr, c->runFront ? (c->runSurface ? "k_front, k_surface" : "k_front")
-                                                        : (c->runSurface ? "k_surface" : "k_vertex"));
-            c->surfaceOff = true;
-            rc = enqueue(c, c->runStream);
-            c->surfaceOff = false;
+                    h.error | h.surfaceErr, c->run.front ? (c->run.surface ? "k_front, k_surface" : "k_front")
+                                                         : (c->run.surface ? "k_surface" : "k_vertex"));
+            rc = enqueue(c, c->runStream, true);
             if (rc != PSGPU_RET_SUCCESS) return rc;
             PSGPU_CHECK(hipStreamSynchronize(c->runStream));
             reran = true;
@@ -1433,8 +1344,8 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
         I.ctFieldMPUs = c->mpuCount ? Q : 0;
         I.ctLaneEvals = 8ull * c->mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
         I.launchFlags = c->mpuCount == 0 ? 0u
-                        : (c->runSplit ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->runSurface ? PSGPU_LAUNCH_SURFACE : 0u) |
-                              (c->runFront ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u);
+                        : (c->run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
+                              (c->run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u);
         c->haveResult = true;
         c->finishedSeq = c->runSeq;
         if (c->countThreads) thread_results_add(c->serial, I.ctMPUs, I.ctSurfaceMPUs);
@@ -2085,7 +1996,7 @@ int psgpu_field_values(psgpu_ctx* c, const float* xyz, uint32_t n, int mode, flo
     PSGPU_CHECK(hipMalloc(&dout, (size_t)n * 4));
     PSGPU_CHECK(hipMalloc(&dcol, (size_t)n * 12));
     PSGPU_CHECK(hipMemcpy(dx, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
-    Params p = make_params(c);
+    Params p = make_params(c, plan_run(c, false));
     hipError_t e;
     if (c->jit) {
         void* args[] = {&p, &dx, &dout, &dcol, &n, &mode};
@@ -2154,7 +2065,7 @@ int psgpu_jit_tier(psgpu_ctx* c) {
 // Generated specialised source for the current model (NUL-terminated, truncated to cap).
 int psgpu_jit_source(psgpu_ctx* c, char* buf, size_t cap) {
     if (!c || !c->haveModel) return PSGPU_RET_PARAM_ERROR;
-    const std::string s = jit_source(c->model, c->tier == 2 || c->useJit == 2, c->treeSplit != 0);
+    const std::string s = jit_source(c->model, c->tier == 2 || c->useJit == 2, c->opt.treeSplit != 0);
     if (buf && cap) {
         const size_t n = std::min(cap - 1, s.size());
         memcpy(buf, s.data(), n);

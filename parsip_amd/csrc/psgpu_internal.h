@@ -13,6 +13,7 @@
 #include "../../include/parsip_gpu.h"
 #include "psgpu_jit.h"
 #include "psgpu_model.h"
+#include "psgpu_plan.h"
 #include "psgpu_pool.h"
 
 namespace psgpu {
@@ -89,29 +90,12 @@ struct psgpu_ctx {
     bool haveModel = false;
     int cull = 1;
     int debug = 0;
-    int vertexBlocksPerCU = 16;  // persistent k_vertex / k_finish grids (256-thread blocks)
-    int finishBlocksPerCU = 8;
-    int finishQuad = 2;  // PSGPU_OPT_FINISH_QUAD: 0 one lane, 1 a quad, 3 a pair of lanes per vertex, 2 by the last run's vertex count
-    int treeSplit = 0;   // PSGPU_OPT_TREE_SPLIT: 1 k_precheck / k_mpu walk the root's two subtrees in two waves
+    psgpu::LaunchOptions opt;  // what plan_launch (psgpu_plan.h) shapes a run by: the launch options,
+    psgpu::LastRun last;       // ... and the last finished run's counts
+    psgpu::LaunchPlan run{};   // the launch shape of the last enqueued run
     bool splittable = false;  // the model's walk splits at the root (jit_splittable)
-    int fusedSurface = 2;     // PSGPU_OPT_FUSED_SURFACE: k_vertex + k_finish in one launch (use_surface)
-    bool runSurface = false;  // the last enqueued run took k_surface
-    int front = 2;            // PSGPU_OPT_FRONT: k_precheck + k_mpu in one launch (use_front)
-    bool runFront = false;    // the last enqueued run took k_front
-    bool runSplit = false;    // ... and the tree-split kernels
-    uint32_t lastSubMax = 0;  // the largest k_front sub-queue of the last finished run (0: none)
     uint32_t* fqReady = nullptr;  // k_front: per queue entry, the tag of the run that published it
     size_t capFq = 0;
-    bool surfaceOff = false;  // while finish re-runs a run whose in-kernel wait gave up: the separate kernels
-    uint32_t splitMaxQueued = 1024;  // PSGPU_OPT_SPLIT_MAX_QUEUED: tree split 2 applies up to this many S2 MPUs
-                                     // (psgpu_create: 4 per CU; C3's 1/8 shares queue ~800, 1/4 ~1,600)
-    uint32_t runMpb = 0;      // k_mpu MPUs per block of the last enqueued run
-    int gridFit = 1;          // k_vertex / k_finish grids sized from the last run's vertices, capped
-                              // at the persistent grids (PSGPU_GRID_FIT=0: the persistent grids;
-                              // C4 1/8 shares -5 %, full grids neutral: profiles/r05_grid_fit_ab2.txt)
-    int mpuMarginDiv = 4;     // k_mpu grid: last run's queued MPUs + 1/this (re-run if short)
-    int vertexWide = 2;  // PSGPU_OPT_VERTEX_WIDE: 0 a quad, 1 one lane per vertex, 2 by the last run's vertex count
-    uint32_t lastV = 0;  // vertices of the last finished run (0: none yet)
     int timing = 0;
     // geometry of the last run
     float cs = 0.0f;
@@ -126,10 +110,7 @@ struct psgpu_ctx {
     uint64_t* pqMask = nullptr;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
     size_t capPqMask = 0;
     uint32_t pShardCap = 0;
-    uint32_t lastQueued = 0;        // S1 survivors queued for S2 in the last finished run
-    bool haveQueued = false;        // lastQueued describes the current range and lattice
     float lastCs = 0.0f;            // the cell size of the last enqueued run
-    uint32_t runMpuBlocks = 0;      // k_mpu grid of the last enqueued run
     uint64_t* scanStatus = nullptr; // 2 x kScanMaxBlocks look-back words (alternating runs)
     uint32_t parity = 0;            // which counter / status set the next run uses
     // runs launched since the counter sets last started at epoch 0 = the next run's epoch
@@ -177,7 +158,7 @@ struct psgpu_ctx {
         hipGraphExec_t exec = nullptr;
         JitKernels* jit = nullptr;
         Params key{};
-        uint32_t shape[6] = {0, 0, 0, 0, 0, 0};
+        psgpu::LaunchPlan plan{};
     } graphs[2];
     float lastMs[kNumKernels] = {};
     PsMeshInfo info{};

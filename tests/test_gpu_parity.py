@@ -645,6 +645,21 @@ def test_graph_replay_and_frames(gpu_poly, oracle):
         gpu_poly.set_option(gpu.OPT_GRAPH, 0)
 
 
+def test_graph_key_holds_the_launch_plan(gpu_poly, oracle):
+    """The replay key is the kernels, the parameters and the launch plan, whose grids follow the
+    last finished run's vertex count: frames 0, 0, 3, 3, 0, 0 of C2 under graph replay, so that
+    each of the two graph slots (they alternate run by run) sees both frames, every run
+    bit-exact to the oracle."""
+    gpu_poly.set_option(gpu.OPT_GRAPH, 1)
+    try:
+        for f in (0, 0, 3, 3, 0, 0):
+            model, cs, _ = synth.make_config("C2", frame=f)
+            gm, gs, om = run_both(gpu_poly, oracle, model, cs)
+            assert_mesh_matches(gm, gs, om)
+    finally:
+        gpu_poly.set_option(gpu.OPT_GRAPH, 0)
+
+
 def test_c5_animation_frame(gpu_poly, oracle):
     """The 512^3, 64-primitive animated workload (C5), one frame against the oracle."""
     model, cs, _ = synth.make_config("C5", frame=7)
