@@ -1699,352 +1699,373 @@ __device__ __forceinline__ void vertex_root(const EdgeSeg& E, uint32_t iv, float
     }
 }
 
-// Vertices: 16 per wavefront pass, one quad of lanes per vertex (vertex first + quad), each
-// walk evaluating one point per lane.
-// Quad pruning: the 4 edge samples e1 + (e2-e1)*(l/3), l = 0..3 (:722-762), then the
-// linear root.  The position goes into the vertex record; k_finish evaluates value,
-// colour and normal there (:764-807) and places the vertex in the mesh.
+// ---------------------------------------------------------------------------
+// Vertex stages.  k_vertex, k_finish and k_surface are compositions of the stages below; each
+// stage exists once, templated on the evaluator and, where the layout matters, on the
+// vertices per wave (VPW):
+//   VPW 16 (quad): 4 lanes per vertex, one point of a walk per lane;
+//   VPW 32 (pair): 2 lanes per vertex, two points per lane (shading only);
+//   VPW 64 (wide): one lane per vertex, its 4 points as one walk.
+// The fewer vertices a wave holds, the shorter its walk: the narrow layouts serve launches
+// whose vertices do not fill the persistent grid (a small rank share), the wide one has more
+// total throughput (packed fp32, one set of uniform work per 4 points) and serves large runs.
+// The launch plan chooses; every layout computes the same bits.
+
+// Stage: the vertex record of a lane.  Batch `batch` of the shard queues holds VPW records, one
+// per group of 64 / VPW lanes.  Lanes past the shard's count take the batch's first record, so
+// that every lane walks a real point, and drop their results (`valid`).
+struct VertexSlot {
+    size_t rec;  // index into p.vk / p.vp
+    bool valid;
+    int j;  // the lane's position in its vertex's lane group
+};
+template <int VPW>
+__device__ __forceinline__ VertexSlot locate_vertex(const Params& p, const ShardBatches& sb, uint32_t batch) {
+    constexpr int kLanes = 64 / VPW;  // lanes per vertex
+    uint32_t shard, first, count;
+    sb.locate(batch, &shard, &first, &count);
+    uint32_t rr = first + (uint32_t)(lane_id() / kLanes);
+    const bool valid = rr < count;
+    if (!valid) rr = first;
+    return VertexSlot{(size_t)shard * p.vShardCap + rr, valid, lane_id() & (kLanes - 1)};
+}
+
+// The quad layouts' exchange: every lane of a quad gets the value of each of its 4 lanes.
+__device__ __forceinline__ void quad_gather(float v, float out[4]) {
+    out[0] = quad_bcast<0>(v);
+    out[1] = quad_bcast<1>(v);
+    out[2] = quad_bcast<2>(v);
+    out[3] = quad_bcast<3>(v);
+}
+
+// The MPU culling mask of a wave's edge samples: every sample lies in its MPU's box (k_mpu's
+// mask; the d^2 >= 1.02 margin absorbs the last-bit rounding of e1 + cs vs lo + 7 cs).
+__device__ __forceinline__ CullMask edge_mask(const Params& p, uint32_t w) {
+    return p.cull ? cull_mask_mpus(p, w) : CullMask{0ull, 0ull};
+}
+
+// Stage: the root's bracket (PS_Polygonizer.cpp:744-755).  The field at the edge's 4 samples,
+// then the first sample whose inside state differs from sample 0, else 3, and the linear
+// root's scale on [sample iv - 1, sample iv]; vertex_root makes the position from the two.
+// Quad: lane j walks sample j, op-box pruning decided per quad (GROUP 4), the 4 values gathered
+// over DPP.  Wide: the lane's 4 samples as one 4-point walk whose pruning groups the lane's 4
+// points (GROUP 0) as the quad layout groups the quad's lanes.
+template <class EV, int VPW>
+__device__ __forceinline__ VertexPos root_bracket(EV& ev, const Params& p, const EdgeSeg& E, const CullMask& cm,
+                                                  const VertexSlot& s) {
+    static_assert(VPW == 16 || VPW == 64, "the root walks one or four samples per lane");
+    float fs[4];
+    if constexpr (VPW == 64) {
+        float xs[4], ys[4], zs[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            xs[l] = edge_sample(E.e[0], E.d[0], l);
+            ys[l] = edge_sample(E.e[1], E.d[1], l);
+            zs[l] = edge_sample(E.e[2], E.d[2], l);
+        }
+        if (p.debug & 256u) {  // ablation bit 8: no phase-A walk
+#pragma unroll
+            for (int l = 0; l < 4; ++l) fs[l] = xs[l];
+        } else {
+            ev.template evaln<0, false, 4>(xs, ys, zs, cm, fs, nullptr);
+        }
+    } else {
+        const float qx = edge_sample(E.e[0], E.d[0], s.j);
+        const float qy = edge_sample(E.e[1], E.d[1], s.j);
+        const float qz = edge_sample(E.e[2], E.d[2], s.j);
+        float f;
+        if (p.debug & 256u) f = qx;  // ablation bit 8: no phase-A walk
+        else f = ev.template eval<4, false>(qx, qy, qz, cm, nullptr);
+        quad_gather(f, fs);
+    }
+    const bool st0 = fs[0] >= 0.5f;
+    const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
+    const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
+    const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
+    return VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
+}
+
+// Stage: colour and unit normal at the root P.  fieldValueAndColor's value and colour walk at P
+// (PS_Polygonizer.cpp:777-778, 1378-1551) and the normal's per-point fieldValue at
+// P + delta e_x, P + delta e_y, P + delta e_z (:780-781, 1598-1622) are four points of one
+// colour walk with per-point pruning (GROUP 1; the colour of points 1-3 is dead code), then
+// the normal -(f(P + delta e_a) - f(P)) / delta and SimdNormalize (rsqrt -> IEEE 1/sqrtf).
+// Quad: lane j walks point j.  Pair: lane j walks points 2j and 2j + 1 and takes its partner's
+// over DPP.  Wide: all four in one lane.  Every lane of a vertex ends with all of S.
+// Culling: a wave whose roots all lie on their bracketing segments (inside their MPUs' boxes;
+// no inf / NaN) takes the MPU masks, whose boxes are grown by delta and so cover every normal
+// sample; any other wave the box of its own points grown by delta.  `mpuMask` is called only in
+// the first case: k_finish loads the masks there, k_surface hands over the bracket's.
+// STAMP (k_finish's wide loop under PSGPU_FIN_PHASES): phases 3, 4 and word 7 for tools/timeline.py.
+struct Shaded {
+    float c[3], n[3];
+};
+template <class EV, int VPW, bool STAMP = false, class MPUMASK>
+__device__ __forceinline__ Shaded shade_vertex(EV& ev, const Params& p, const float P[3], bool onSeg,
+                                               const VertexSlot& s, MPUMASK mpuMask) {
+    const float delta = 0.001f;
+    const float inv = -1.0f / delta;
+    Shaded S{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    if (p.debug & 32u) return S;  // ablation bit 5: no walks
+    CullMask cm{0ull, 0ull};
+    if (p.cull) {
+        if (ballot(!onSeg) == 0ull) cm = mpuMask();
+        else cm = cull_mask_points(as_const(p.model), P[0], P[1], P[2], true, delta);
+    }
+    if constexpr (STAMP) {
+        phase_stamp_after(p, 3, 2048u, __uint_as_float((uint32_t)(cm.lo ^ cm.hi)));
+#if PSGPU_FIN_PHASES
+        const uint64_t nvalid = (uint64_t)__popcll(ballot(s.valid));
+        if ((p.debug & 2048u) && p.stamps && lane_id() == 0) {  // phase word 7: live primitives, vertices
+            const uint32_t sw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+            if (sw < p.stampCap)
+                p.stamps[3 * (size_t)kNumStampKernels * p.stampCap + 8 * (size_t)sw + 7] =
+                    (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | (nvalid << 16);
+        }
+#endif
+    }
+    float g[4];  // the field at the four points
+    if constexpr (VPW == 16) {
+        const float qx = s.j == 1 ? P[0] + delta : P[0];
+        const float qy = s.j == 2 ? P[1] + delta : P[1];
+        const float qz = s.j == 3 ? P[2] + delta : P[2];
+        float c4[3];
+        const float f = ev.template eval<1, true>(qx, qy, qz, cm, c4);
+        S.c[0] = quad_bcast<0>(c4[0]);
+        S.c[1] = quad_bcast<0>(c4[1]);
+        S.c[2] = quad_bcast<0>(c4[2]);
+        quad_gather(f, g);
+    } else if constexpr (VPW == 32) {
+        // lane 0: P, P + delta e_x; lane 1: P + delta e_y, P + delta e_z
+        const float qx[2] = {P[0], s.j == 0 ? P[0] + delta : P[0]};
+        const float qy[2] = {s.j == 1 ? P[1] + delta : P[1], P[1]};
+        const float qz[2] = {P[2], s.j == 1 ? P[2] + delta : P[2]};
+        float f[2], c6[6];
+        ev.template evaln<1, true, 2>(qx, qy, qz, cm, f, c6);
+        const float o0 = PSGPU_DPP_F(f[0], 0xB1), o1 = PSGPU_DPP_F(f[1], 0xB1);
+        const float oc0 = PSGPU_DPP_F(c6[0], 0xB1), oc1 = PSGPU_DPP_F(c6[1], 0xB1),
+                    oc2 = PSGPU_DPP_F(c6[2], 0xB1);
+        S.c[0] = s.j == 0 ? c6[0] : oc0;
+        S.c[1] = s.j == 0 ? c6[1] : oc1;
+        S.c[2] = s.j == 0 ? c6[2] : oc2;
+        g[0] = s.j == 0 ? f[0] : o0;
+        g[1] = s.j == 0 ? f[1] : o1;
+        g[2] = s.j == 0 ? o0 : f[0];
+        g[3] = s.j == 0 ? o1 : f[1];
+    } else {
+        const float qx[4] = {P[0], P[0] + delta, P[0], P[0]};
+        const float qy[4] = {P[1], P[1], P[1] + delta, P[1]};
+        const float qz[4] = {P[2], P[2], P[2], P[2] + delta};
+        float c4[12];
+        ev.template evaln<1, true, 4>(qx, qy, qz, cm, g, c4);
+        if constexpr (STAMP) phase_stamp_after(p, 4, 2048u, g[0] + g[1] + g[2] + g[3] + c4[0] + c4[1] + c4[2]);
+        S.c[0] = c4[0];
+        S.c[1] = c4[1];
+        S.c[2] = c4[2];
+    }
+    const float nx = (g[1] - g[0]) * inv;
+    const float ny = (g[2] - g[0]) * inv;
+    const float nz = (g[3] - g[0]) * inv;
+    const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
+    S.n[0] = nx * im;
+    S.n[1] = ny * im;
+    S.n[2] = nz * im;
+    return S;
+}
+
+// Stage: the vertex into the compact mesh at index gi.  Quad: lanes 0-2 write component j of
+// position, normal and colour.  Pair: lane j writes component j, lane 0 also component 2.
+// Wide: the lane writes all nine.  Past vCap nothing is written: finish() grows and re-runs.
+// (values, not references into S: a choice between addresses would keep S in scratch memory)
+__device__ __forceinline__ float component(int j, float x, float y, float z) { return j == 0 ? x : (j == 1 ? y : z); }
+template <int VPW>
+__device__ __forceinline__ void store_vertex(const Params& p, const VertexSlot& s, uint32_t gi, const float P[3],
+                                             const Shaded& S) {
+    if (!s.valid || gi >= p.vCap) return;
+    if constexpr (VPW == 16) {
+        if (s.j < 3) {
+            const uint32_t o = gi * 3 + (uint32_t)s.j;
+            p.pos[o] = component(s.j, P[0], P[1], P[2]);
+            p.nrm[o] = component(s.j, S.n[0], S.n[1], S.n[2]);
+            p.col[o] = component(s.j, S.c[0], S.c[1], S.c[2]);
+        }
+    } else if constexpr (VPW == 32) {
+        const uint32_t o = gi * 3 + (uint32_t)s.j;
+        p.pos[o] = s.j == 0 ? P[0] : P[1];
+        p.nrm[o] = s.j == 0 ? S.n[0] : S.n[1];
+        p.col[o] = s.j == 0 ? S.c[0] : S.c[1];
+        if (s.j == 0) {
+            p.pos[gi * 3 + 2] = P[2];
+            p.nrm[gi * 3 + 2] = S.n[2];
+            p.col[gi * 3 + 2] = S.c[2];
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.pos[gi * 3 + c] = P[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.nrm[gi * 3 + c] = S.n[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.col[gi * 3 + c] = S.c[c];
+    }
+}
+
+// k_surface's wait for the offsets scan (every scan block released its offsets), bounded: a
+// broken protocol flags the run (error bit 1) instead of hanging the device.
+// The flag reaches the host through words block 0 never overwrites (surfaceErr, raised with
+// a plain store; totals[7], raised atomically), so a timeout after block 0 published the
+// counters still fails the run, and psgpu_finish re-runs it as k_vertex + k_finish.
+__device__ __forceinline__ void surface_wait_scan(const Params& p) {
+    if (lane_id() == 0) {
+        uint32_t spins = 0;
+        // test hook (PSGPU_OPT_DEBUG bit 25): a bound far below the scan blocks' delay
+        const uint32_t bound = (p.debug & (1u << 25)) ? 4u : (1u << 22);
+        while (__hip_atomic_load(&p.ctr->scanDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.scanBlocks) {
+            __builtin_amdgcn_s_sleep(2);
+            if (++spins > bound) {
+                atomicOr(&p.ctr->error, 2u);
+                atomicOr(&p.totals[7], 2u);
+                p.hostCtr->surfaceErr = 2u;
+                __threadfence_system();
+                break;
+            }
+        }
+    }
+    // no agent-scope acquire here: on gfx950 it invalidates the XCD's L2 for every kernel on it
+    // (measured: a 1/8 share 0.028 vs 0.015 ms/step).  The offsets are read with agent-scope
+    // loads instead (surface_offs), which bypass the non-coherent caches and are issued only
+    // after the flag was seen.
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+}
+// an offsets word written by this launch's scan blocks (released before their scanDone count)
+__device__ __forceinline__ uint64_t surface_offs(const Params& p, uint32_t i) {
+    return __hip_atomic_load(&p.offs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// An offsets word of either kernel: k_finish runs after the launch that scanned them and loads
+// plainly; k_surface (FUSED) reads what its own scan blocks wrote.
+template <bool FUSED>
+__device__ __forceinline__ uint64_t offs_word(const Params& p, uint32_t i) {
+    if constexpr (FUSED) return surface_offs(p, i);
+    else return p.offs[i];
+}
+
+// Stage: block 0's duties at the end of a run.  The run's counters to the host (mapped pinned
+// memory), then -- after a system fence, so the host never sees a reset it could mistake for
+// this run's -- the next run's counters and offsets-scan words (no kernel of this run touches
+// them), and the run's totals for the count exchange between parts (RCCL).
+// FUSED (k_surface, called once every scan block is done): `error` is read at agent scope, so a
+// look-back timeout of any scan block (error bit 0) is in what is published; the host's
+// surfaceErr word is never overwritten and totals[7] is raised, never stored (k_precheck zeroed
+// it), so a scan-wait timeout flagged by another wave after this survives (surface_wait_scan).
+template <bool FUSED>
+__device__ __forceinline__ void publish_run(const Params& p) {
+    constexpr uint32_t kWords = sizeof(DevCounters) / 4;
+    constexpr uint32_t kErrWord = __builtin_offsetof(DevCounters, error) / 4;
+    constexpr uint32_t kSurfWord = __builtin_offsetof(DevCounters, surfaceErr) / 4;
+    constexpr uint32_t kEpochWord = __builtin_offsetof(DevCounters, epoch) / 4;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(p.ctr);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(p.hostCtr);
+    uint32_t err = 0u;  // FUSED: read once; the host's copy and totals[7] get this value
+    if constexpr (FUSED) err = __hip_atomic_load(&p.ctr->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t i = threadIdx.x; i < kWords; i += blockDim.x)
+        if (!FUSED || i != kSurfWord) dst[i] = FUSED && i == kErrWord ? err : src[i];
+    __threadfence_system();
+    uint32_t* nx = reinterpret_cast<uint32_t*>(p.ctrNext);
+    const uint32_t nextEpoch = p.ctr->epoch + 1u;
+    for (uint32_t i = threadIdx.x; i < kWords; i += blockDim.x)
+        nx[i] = i == 0 ? 0x7fffffffu : (i == kEpochWord ? nextEpoch : 0u);
+    for (uint32_t i = threadIdx.x; i < kScanMaxBlocks; i += blockDim.x) p.scanStatusNext[i] = 0ull;
+    if (threadIdx.x < 64) {
+        const ShardCtr& sc = p.ctr->shard[threadIdx.x];
+        const uint32_t tv = wave_sum(sc.v), tt = wave_sum(sc.t), tp = wave_sum(sc.p), tb = wave_sum(sc.b),
+                       ts = wave_sum(sc.s);
+        if (threadIdx.x == 0) {
+            const uint32_t tot[8] = {p.mpuCount, tv, tt, tp + tb, ts, tp, (uint32_t)p.ctr->firstOverflow,
+                                     FUSED ? err : p.ctr->error};
+            for (int i = 0; i < (FUSED ? 7 : 8); ++i) p.totals[i] = tot[i];
+            if (FUSED && err) atomicOr(&p.totals[7], err);
+        }
+    }
+}
+
+// Stage: triangle records -> global vertex ids.  A record holds three 11-bit MPU-local vertex
+// ids and its local triangle id; its MPU's offsets word gives the bases of both.  Past tCap
+// nothing is written: finish() grows and re-runs.
+template <bool FUSED>
+__device__ __forceinline__ void triangle_pass(const Params& p, const ShardBatches& sb, uint32_t wave0,
+                                              uint32_t nWaves) {
+    for (uint32_t batch = wave0; batch < sb.total; batch += nWaves) {
+        uint32_t shard, first, count;
+        sb.locate(batch, &shard, &first, &count);
+        const uint32_t t = first + lane_id();
+        if (t >= count) continue;
+        const TriRec R = p.tq[(size_t)shard * p.tShardCap + t];
+        const uint64_t o = offs_word<FUSED>(p, ((R.a >> 12) << 6) | shard);  // the record's shard is w & 63
+        const uint32_t gt = (uint32_t)(o >> 32) + (R.a & 2047u);
+        const uint32_t base = (uint32_t)o;
+        if (gt >= p.tCap) continue;
+        p.tris[gt * 3 + 0] = base + (R.b & 2047u);
+        p.tris[gt * 3 + 1] = base + ((R.b >> 11) & 2047u);
+        p.tris[gt * 3 + 2] = base + ((R.b >> 22) | (((R.a >> 11) & 1u) << 10));
+    }
+}
+
+// k_vertex: the first blocks scan the offsets (scan_counts_block); every wave then brackets
+// the roots of its batches of vertex records, quad or wide, and stores bracket and scale into
+// the record.  k_finish recomputes the position from them (vertex_root).
 template <class EV, int VPW = 16>
 __device__ __forceinline__ void vertex_body(const Params& p, float* lds) {
     const int wave = wave_index();
-    const int lane = lane_id();
-    ModelPtr M = as_const(p.model);
-    EV ev(M, lds + wave * (p.slotsPerLane * 4 * 64) + lane);
-    const int j = lane & 3;
+    EV ev(as_const(p.model), lds + wave * (p.slotsPerLane * 4 * 64) + lane_id());
     if (blockIdx.x < p.scanBlocks) scan_counts_block(p, blockIdx.x);  // block-uniform
     __shared__ uint32_t sCnt[kShards];
     stage_shard_counts(p, 1, sCnt);  // ShardCtr::v
     __syncthreads();
     const uint32_t nWaves = gridDim.x * (blockDim.x >> 6);
-if constexpr (VPW == 64) {
-    // one lane per vertex: its 4 edge samples as one 4-point walk whose op-box pruning
-    // groups the lane's 4 points (GROUP 0) as the quad layout groups the quad's lanes, so
-    // every value is the same; packed fp32 and one set of uniform work per 4 samples
-    // (more total throughput, a 4x longer walk per wave: chosen for large runs)
-    const ShardBatches sb(sCnt, p.vShardCap, 64);
+    const ShardBatches sb(sCnt, p.vShardCap, VPW);
     for (uint32_t batch = blockIdx.x * (blockDim.x >> 6) + wave; batch < sb.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sb.locate(batch, &shard, &first, &count);
-        uint32_t rr = first + (uint32_t)lane;
-        const bool valid = rr < count;
-        if (!valid) rr = first;
-        const size_t rec = (size_t)shard * p.vShardCap + rr;
-        const VertexKey R = p.vk[rec];
-        const EdgeSeg E = edge_segment(p, R.w, R.vidKey >> 16);
-        float xs[4], ys[4], zs[4], fs[4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-            xs[s2] = edge_sample(E.e[0], E.d[0], s2);
-            ys[s2] = edge_sample(E.e[1], E.d[1], s2);
-            zs[s2] = edge_sample(E.e[2], E.d[2], s2);
-        }
-        CullMask cm{0ull, 0ull};
-        if (p.cull) cm = cull_mask_mpus(p, R.w);
-        if (p.debug & 256u) {  // ablation bit 8: no phase-A walk
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) fs[s2] = xs[s2];
-        } else {
-            ev.template evaln<0, false, 4>(xs, ys, zs, cm, fs, nullptr);
-        }
-        // first sample whose inside state differs from sample 0, else 3 (:744-755); the
-        // root itself is k_finish's (vertex_root)
-        const bool st0 = fs[0] >= 0.5f;
-        const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
-        const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
-        const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
-        if (valid) p.vp[rec] = VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
+        const VertexSlot s = locate_vertex<VPW>(p, sb, batch);
+        const VertexKey K = p.vk[s.rec];
+        const VertexPos R =
+            root_bracket<EV, VPW>(ev, p, edge_segment(p, K.w, K.vidKey >> 16), edge_mask(p, K.w), s);
+        if (s.valid && s.j == 0) p.vp[s.rec] = R;
     }
-} else {
-    const ShardBatches sb(sCnt, p.vShardCap, 16);
-    for (uint32_t batch = blockIdx.x * (blockDim.x >> 6) + wave; batch < sb.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sb.locate(batch, &shard, &first, &count);
-        uint32_t rr = first + ((uint32_t)lane >> 2);
-        const bool valid = rr < count;
-        if (!valid) rr = first;
-        const size_t rec = (size_t)shard * p.vShardCap + rr;
-        const VertexKey R = p.vk[rec];
-        const EdgeSeg E = edge_segment(p, R.w, R.vidKey >> 16);
-        const float qx = edge_sample(E.e[0], E.d[0], j);  // lane j of the quad: sample j
-        const float qy = edge_sample(E.e[1], E.d[1], j);
-        const float qz = edge_sample(E.e[2], E.d[2], j);
-        // every edge sample lies in its MPU's box (k_mpu's mask; the d^2 >= 1.02 margin
-        // absorbs the last-bit rounding of e1 + cs vs lo + 7 cs)
-        CullMask cm{0ull, 0ull};
-        if (p.cull) cm = cull_mask_mpus(p, R.w);
-        float f;
-        if (p.debug & 256u) {  // ablation bit 8: no phase-A walk
-            f = qx;
-        } else {
-            ev.template evaln<4, false, 1>(&qx, &qy, &qz, cm, &f, nullptr);
-        }
-        float fs[4];
-        fs[0] = quad_bcast<0>(f);
-        fs[1] = quad_bcast<1>(f);
-        fs[2] = quad_bcast<2>(f);
-        fs[3] = quad_bcast<3>(f);
-        // first sample whose inside state differs from sample 0, else 3 (:744-755)
-        const bool st0 = fs[0] >= 0.5f;
-        const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
-        const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
-        const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
-        // into the record; k_finish recomputes the root there (vertex_root) and adds
-        // normal and colour
-        if (valid && j == 0) p.vp[rec] = VertexPos{(0.5f - fa) / (fb - fa), (uint32_t)iv};
-    }
-}
 }
 
-// Finish: per vertex fieldValueAndColor's value and colour walk (PS_Polygonizer.cpp:777-778,
-// 1378-1551) and the three normal samples (:780-781, 1598-1622), then the triangle records
-// -> global vertex ids.  Runs after k_vertex wrote the roots.  VPW 64: one lane per
-// vertex walking its 4 points; VPW 16: a quad of lanes per vertex, one point each (a
-// quarter of the walk per wave: shorter spans when the vertices do not fill the persistent
-// grid, e.g. a small rank share; more total work otherwise).  Same values either way.
+// k_finish, after k_vertex wrote the roots: block 0 publishes the run; every wave then shades
+// the vertices of its batches of records (wide, quad or pair) into the mesh, then resolves its
+// batches of triangle records.
+// PSGPU_FIN_PHASES stamps the wide loop only: 2 = records in and root recomputed, 3-4 inside
+// shade_vertex, 5 = stored.
 template <class EV, int VPW = 64>
 __device__ __forceinline__ void finish_body(const Params& p, float* lds) {
+    constexpr bool kStamp = VPW == 64;
     const int wave = wave_index();
-    const int lane = lane_id();
-    ModelPtr M = as_const(p.model);
-    EV ev(M, lds + wave * (p.slotsPerLane * 4 * 64) + lane);
+    EV ev(as_const(p.model), lds + wave * (p.slotsPerLane * 4 * 64) + lane_id());
     const uint32_t nWaves = gridDim.x * (blockDim.x >> 6);
     const uint32_t wave0 = blockIdx.x * (blockDim.x >> 6) + wave;
-    const float delta = 0.001f;
-    const float inv = -1.0f / delta;
     phase_stamp_after(p, 0, 2048u, 0.0f);
-    if (blockIdx.x == 0) {  // the run's counters for the host (mapped pinned memory)
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(p.ctr);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(p.hostCtr);
-        for (uint32_t i = threadIdx.x; i < sizeof(DevCounters) / 4; i += blockDim.x) dst[i] = src[i];
-        __threadfence_system();
-        // the next run's counters and offsets-scan words (no kernel of this run touches them)
-        uint32_t* nx = reinterpret_cast<uint32_t*>(p.ctrNext);
-        const uint32_t nextEpoch = p.ctr->epoch + 1u;
-        constexpr uint32_t kEpochWord = __builtin_offsetof(DevCounters, epoch) / 4;
-        for (uint32_t i = threadIdx.x; i < sizeof(DevCounters) / 4; i += blockDim.x)
-            nx[i] = i == 0 ? 0x7fffffffu : (i == kEpochWord ? nextEpoch : 0u);
-        for (uint32_t i = threadIdx.x; i < kScanMaxBlocks; i += blockDim.x) p.scanStatusNext[i] = 0ull;
-        if (threadIdx.x < 64) {  // the run's totals for the count exchange between parts (RCCL)
-            const ShardCtr& sc = p.ctr->shard[threadIdx.x];
-            const uint32_t tv = wave_sum(sc.v), tt = wave_sum(sc.t), tp = wave_sum(sc.p), tb = wave_sum(sc.b),
-                           ts = wave_sum(sc.s);
-            if (threadIdx.x == 0) {
-                const uint32_t tot[8] = {p.mpuCount, tv, tt, tp + tb, ts, tp, (uint32_t)p.ctr->firstOverflow,
-                                         p.ctr->error};
-                for (int i = 0; i < 8; ++i) p.totals[i] = tot[i];
-            }
-        }
-    }
+    if (blockIdx.x == 0) publish_run<false>(p);
     __shared__ uint32_t sCnt[2 * kShards];
     stage_shard_counts(p, 1, sCnt);            // ShardCtr::v
     stage_shard_counts(p, 2, sCnt + kShards);  // ShardCtr::t
     __syncthreads();
     phase_stamp_after(p, 1, 2048u, 0.0f);
-if constexpr (VPW == 16) {
-    // a quad of lanes per vertex: lane j of the quad walks point j (p, p + delta e_x,
-    // p + delta e_y, p + delta e_z) with the same per-point pruning (GROUP 1) as the
-    // 4-point walk below, so every value is the same; lanes 0-2 of the quad then write
-    // component j of position, normal and colour
-    const ShardBatches sv(sCnt, p.vShardCap, 16);
-    const int qj = lane & 3;
+    const ShardBatches sv(sCnt, p.vShardCap, VPW);
     for (uint32_t batch = wave0; batch < sv.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sv.locate(batch, &shard, &first, &count);
-        uint32_t rec = first + (uint32_t)(lane >> 2);
-        const bool valid = rec < count;
-        if (!valid) rec = first;
-        const size_t ri = (size_t)shard * p.vShardCap + rec;
-        const VertexKey K = p.vk[ri];
-        const VertexPos R = p.vp[ri];
-        const uint32_t gi = (uint32_t)p.offs[K.w] + (K.vidKey & 0xffffu);
-        float P[3];  // the root, recomputed from k_vertex's record with its expressions
+        const VertexSlot s = locate_vertex<VPW>(p, sv, batch);
+        const VertexKey K = p.vk[s.rec];
+        const VertexPos R = p.vp[s.rec];
+        const uint32_t gi = (uint32_t)offs_word<false>(p, K.w) + (K.vidKey & 0xffffu);
+        float P[3];
         vertex_root(edge_segment(p, K.w, K.vidKey >> 16), R.iv, R.scale, P);
-        // on its bracketing segment: inside the MPU box (no inf / NaN)
-        const bool onSeg = R.scale >= 0.0f && R.scale <= 1.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f};
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (!(p.debug & 32u)) {  // ablation bit 5: no walks
-            CullMask cm{0ull, 0ull};
-            if (p.cull) {
-                if (ballot(!onSeg) == 0ull) cm = cull_mask_mpus(p, K.w);
-                else cm = cull_mask_points(M, P[0], P[1], P[2], true, delta);
-            }
-            const float qx = qj == 1 ? P[0] + delta : P[0];
-            const float qy = qj == 2 ? P[1] + delta : P[1];
-            const float qz = qj == 3 ? P[2] + delta : P[2];
-            float c4[3];
-            const float g = ev.template eval<1, true>(qx, qy, qz, cm, c4);
-            c[0] = quad_bcast<0>(c4[0]);
-            c[1] = quad_bcast<0>(c4[1]);
-            c[2] = quad_bcast<0>(c4[2]);
-            const float vtx = quad_bcast<0>(g);
-            nx = (quad_bcast<1>(g) - vtx) * inv;
-            ny = (quad_bcast<2>(g) - vtx) * inv;
-            nz = (quad_bcast<3>(g) - vtx) * inv;
-            const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
-            nx = nx * im;
-            ny = ny * im;
-            nz = nz * im;
-        }
-        if (valid && qj < 3 && gi < p.vCap) {  // past vCap: finish() grows and re-runs
-            const uint32_t o = gi * 3 + (uint32_t)qj;
-            p.pos[o] = qj == 0 ? P[0] : (qj == 1 ? P[1] : P[2]);
-            p.nrm[o] = qj == 0 ? nx : (qj == 1 ? ny : nz);
-            p.col[o] = qj == 0 ? c[0] : (qj == 1 ? c[1] : c[2]);
-        }
+        if constexpr (kStamp) phase_stamp_after(p, 2, 2048u, P[0] + P[1] + P[2]);
+        const Shaded S = shade_vertex<EV, VPW, kStamp>(ev, p, P, R.scale >= 0.0f && R.scale <= 1.0f, s,
+                                                       [&] { return cull_mask_mpus(p, K.w); });
+        store_vertex<VPW>(p, s, gi, P, S);
+        if constexpr (kStamp) phase_stamp_after(p, 5, 2048u, __uint_as_float(gi));
     }
-} else if constexpr (VPW == 32) {
-    // a pair of lanes per vertex: lane j of the pair walks points 2j, 2j + 1 of
-    // {p, p + delta e_x, p + delta e_y, p + delta e_z} (per-point pruning, as above); the
-    // partner's two values come over DPP; lane j writes component j, lane 0 also component 2
-    const ShardBatches sv(sCnt, p.vShardCap, 32);
-    const int pj = lane & 1;
-    for (uint32_t batch = wave0; batch < sv.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sv.locate(batch, &shard, &first, &count);
-        uint32_t rec = first + (uint32_t)(lane >> 1);
-        const bool valid = rec < count;
-        if (!valid) rec = first;
-        const size_t ri = (size_t)shard * p.vShardCap + rec;
-        const VertexKey K = p.vk[ri];
-        const VertexPos R = p.vp[ri];
-        const uint32_t gi = (uint32_t)p.offs[K.w] + (K.vidKey & 0xffffu);
-        float P[3];  // the root, recomputed from k_vertex's record with its expressions
-        vertex_root(edge_segment(p, K.w, K.vidKey >> 16), R.iv, R.scale, P);
-        // on its bracketing segment: inside the MPU box (no inf / NaN)
-        const bool onSeg = R.scale >= 0.0f && R.scale <= 1.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f};
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (!(p.debug & 32u)) {  // ablation bit 5: no walks
-            CullMask cm{0ull, 0ull};
-            if (p.cull) {
-                if (ballot(!onSeg) == 0ull) cm = cull_mask_mpus(p, K.w);
-                else cm = cull_mask_points(M, P[0], P[1], P[2], true, delta);
-            }
-            // lane 0: p, p + delta e_x; lane 1: p + delta e_y, p + delta e_z
-            const float qx[2] = {P[0], pj == 0 ? P[0] + delta : P[0]};
-            const float qy[2] = {pj == 1 ? P[1] + delta : P[1], P[1]};
-            const float qz[2] = {P[2], pj == 1 ? P[2] + delta : P[2]};
-            float g[2], c6[6];
-            ev.template evaln<1, true, 2>(qx, qy, qz, cm, g, c6);
-            const float o0 = PSGPU_DPP_F(g[0], 0xB1), o1 = PSGPU_DPP_F(g[1], 0xB1);
-            const float oc0 = PSGPU_DPP_F(c6[0], 0xB1), oc1 = PSGPU_DPP_F(c6[1], 0xB1),
-                        oc2 = PSGPU_DPP_F(c6[2], 0xB1);
-            c[0] = pj == 0 ? c6[0] : oc0;
-            c[1] = pj == 0 ? c6[1] : oc1;
-            c[2] = pj == 0 ? c6[2] : oc2;
-            const float vtx = pj == 0 ? g[0] : o0;
-            const float g1 = pj == 0 ? g[1] : o1;
-            const float g2 = pj == 0 ? o0 : g[0];
-            const float g3 = pj == 0 ? o1 : g[1];
-            nx = (g1 - vtx) * inv;
-            ny = (g2 - vtx) * inv;
-            nz = (g3 - vtx) * inv;
-            const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
-            nx = nx * im;
-            ny = ny * im;
-            nz = nz * im;
-        }
-        if (valid && gi < p.vCap) {  // past vCap: finish() grows and re-runs
-            const uint32_t o = gi * 3 + (uint32_t)pj;
-            p.pos[o] = pj == 0 ? P[0] : P[1];
-            p.nrm[o] = pj == 0 ? nx : ny;
-            p.col[o] = pj == 0 ? c[0] : c[1];
-            if (pj == 0) {
-                p.pos[gi * 3 + 2] = P[2];
-                p.nrm[gi * 3 + 2] = nz;
-                p.col[gi * 3 + 2] = c[2];
-            }
-        }
-    }
-} else {
-    const ShardBatches sv(sCnt, p.vShardCap, 64);
-    for (uint32_t batch = wave0; batch < sv.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sv.locate(batch, &shard, &first, &count);
-        uint32_t rec = first + (uint32_t)lane;
-        const bool valid = rec < count;
-        if (!valid) rec = first;
-        const size_t ri = (size_t)shard * p.vShardCap + rec;
-        const VertexKey K = p.vk[ri];
-        const VertexPos R = p.vp[ri];
-        const uint32_t gi = (uint32_t)p.offs[K.w] + (K.vidKey & 0xffffu);
-        float P[3];  // the root, recomputed from k_vertex's record with its expressions
-        vertex_root(edge_segment(p, K.w, K.vidKey >> 16), R.iv, R.scale, P);
-        // on its bracketing segment: inside the MPU box (no inf / NaN)
-        const bool onSeg = R.scale >= 0.0f && R.scale <= 1.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f};
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        phase_stamp_after(p, 2, 2048u, P[0] + P[1] + P[2]);  // records in, root recomputed
-        if (!(p.debug & 32u)) {  // ablation bit 5: no walks
-            // vertices on their segments: the MPU masks (boxes grown by delta) cover p and
-            // every normal sample; otherwise the wave's own box grown by delta
-            CullMask cm{0ull, 0ull};
-            if (p.cull) {
-                if (ballot(!onSeg) == 0ull) cm = cull_mask_mpus(p, K.w);
-                else cm = cull_mask_points(M, P[0], P[1], P[2], true, delta);
-            }
-            phase_stamp_after(p, 3, 2048u, __uint_as_float((uint32_t)(cm.lo ^ cm.hi)));
-#if PSGPU_FIN_PHASES
-            const uint64_t nvalid = (uint64_t)__popcll(ballot(valid));
-            if ((p.debug & 2048u) && p.stamps && lane == 0) {  // phase word 7: live primitives, vertices
-                const uint32_t sw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-                if (sw < p.stampCap)
-                    p.stamps[3 * (size_t)kNumStampKernels * p.stampCap + 8 * (size_t)sw + 7] =
-                        (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | (nvalid << 16);
-            }
-#endif
-            // value + colour at p and the normal's per-point fieldValue at p + delta*e_a
-            // (:1598-1622) as four points of one walk (the colour of points 1-3 is dead
-            // code); then SimdNormalize (rsqrt -> IEEE 1/sqrtf)
-            const float qx[4] = {P[0], P[0] + delta, P[0], P[0]};
-            const float qy[4] = {P[1], P[1], P[1] + delta, P[1]};
-            const float qz[4] = {P[2], P[2], P[2], P[2] + delta};
-            float g[4], c4[12];
-            ev.template evaln<1, true, 4>(qx, qy, qz, cm, g, c4);
-            phase_stamp_after(p, 4, 2048u, g[0] + g[1] + g[2] + g[3] + c4[0] + c4[1] + c4[2]);
-            c[0] = c4[0];
-            c[1] = c4[1];
-            c[2] = c4[2];
-            const float vtx = g[0];
-            nx = (g[1] - vtx) * inv;
-            ny = (g[2] - vtx) * inv;
-            nz = (g[3] - vtx) * inv;
-            const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
-            nx = nx * im;
-            ny = ny * im;
-            nz = nz * im;
-        }
-        if (valid && gi < p.vCap) {  // past vCap: finish() grows and re-runs
-            p.pos[gi * 3 + 0] = P[0];
-            p.pos[gi * 3 + 1] = P[1];
-            p.pos[gi * 3 + 2] = P[2];
-            p.nrm[gi * 3 + 0] = nx;
-            p.nrm[gi * 3 + 1] = ny;
-            p.nrm[gi * 3 + 2] = nz;
-            p.col[gi * 3 + 0] = c[0];
-            p.col[gi * 3 + 1] = c[1];
-            p.col[gi * 3 + 2] = c[2];
-        }
-        phase_stamp_after(p, 5, 2048u, __uint_as_float(gi));
-    }
-}
     if (p.debug & 64u) return;  // ablation bit 6: no triangles
-    const ShardBatches sb(sCnt + kShards, p.tShardCap, 64);
-    for (uint32_t batch = wave0; batch < sb.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sb.locate(batch, &shard, &first, &count);
-        const uint32_t t = first + lane;
-        if (t >= count) continue;
-        const TriRec R = p.tq[(size_t)shard * p.tShardCap + t];
-        const uint64_t o = p.offs[((R.a >> 12) << 6) | shard];  // the record's shard is w & 63
-        const uint32_t gt = (uint32_t)(o >> 32) + (R.a & 2047u);
-        const uint32_t base = (uint32_t)o;
-        if (gt >= p.tCap) continue;  // finish() grows and re-runs
-        p.tris[gt * 3 + 0] = base + (R.b & 2047u);
-        p.tris[gt * 3 + 1] = base + ((R.b >> 11) & 2047u);
-        p.tris[gt * 3 + 2] = base + ((R.b >> 22) | (((R.a >> 11) & 1u) << 10));
-    }
+    triangle_pass<false>(p, ShardBatches(sCnt + kShards, p.tShardCap, 64), wave0, nWaves);
     phase_stamp_after(p, 6, 2048u, 0.0f);
 }
 
@@ -2088,60 +2109,21 @@ __device__ __forceinline__ void front_body(const Params& p, unsigned char* smem)
     }
 }
 
-// k_surface's wait for the offsets scan (every scan block released its offsets), bounded: a
-// broken protocol flags the run (error bit 1) instead of hanging the device.
-// The flag reaches the host through words block 0 never overwrites (surfaceErr, raised with
-// a plain store; totals[7], raised atomically), so a timeout after block 0 published the
-// counters still fails the run, and psgpu_finish re-runs it as k_vertex + k_finish.
-__device__ __forceinline__ void surface_wait_scan(const Params& p) {
-    if (lane_id() == 0) {
-        uint32_t spins = 0;
-        // test hook (PSGPU_OPT_DEBUG bit 25): a bound far below the scan blocks' delay
-        const uint32_t bound = (p.debug & (1u << 25)) ? 4u : (1u << 22);
-        while (__hip_atomic_load(&p.ctr->scanDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.scanBlocks) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > bound) {
-                atomicOr(&p.ctr->error, 2u);
-                atomicOr(&p.totals[7], 2u);
-                p.hostCtr->surfaceErr = 2u;
-                __threadfence_system();
-                break;
-            }
-        }
-    }
-    // no agent-scope acquire here: on gfx950 it invalidates the XCD's L2 for every kernel on it
-    // (measured: a 1/8 share 0.028 vs 0.015 ms/step).  The offsets are read with agent-scope
-    // loads instead (surface_offs), which bypass the non-coherent caches and are issued only
-    // after the flag was seen.
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
-// an offsets word written by this launch's scan blocks (released before their scanDone count)
-__device__ __forceinline__ uint64_t surface_offs(const Params& p, uint32_t i) {
-    return __hip_atomic_load(&p.offs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // k_surface (PSGPU_OPT_FUSED_SURFACE): k_vertex and k_finish in one launch for small launches
-// (a rank's share; the launch floor, not the work, sets their step: DESIGN.md §5).  A quad of
-// lanes per vertex for both walks -- the root's 4 edge samples (k_vertex's quad layout), then
-// value + colour at the root and its 3 normal samples (k_finish's quad layout) -- with the
-// root's bracket and scale kept in registers instead of the vertex record.  The first blocks
-// run the offsets scan as in k_vertex and release it; a wave waits for every scan block only
-// before its first mesh write.  Same values as the two kernels: the same expressions on the
-// same records and the same culling masks.  The scan blocks have the lowest block ids, so they
-// are dispatched before any waiting block of their XCD: the wait cannot starve them.
-// VPW 64 (k_surface_w, PSGPU_OPT_FUSED_SURFACE 3): one lane per vertex for both walks -- the root's
-// 4 edge samples as k_vertex's wide layout walks them, then value + colour and the 3 normal samples
-// as k_finish's 64-vertex layout -- for launches whose vertices fill the device.
+// (a rank's share; the launch floor, not the work, sets their step: DESIGN.md §5), quad layout;
+// k_surface_w (PSGPU_OPT_FUSED_SURFACE 3, VPW 64): the wide layout, for launches whose vertices
+// fill the device.  Per vertex the stages of both kernels in one loop, with the root's bracket
+// and scale kept in registers instead of the vertex record, and the bracket's MPU masks reused
+// for the shading.  The first blocks run the offsets scan as in k_vertex and release it; block 0
+// publishes the run once every scan block is done; any other wave waits for the scan only before
+// its first mesh write.  The scan blocks have the lowest block ids, so they are dispatched before
+// any waiting block of their XCD: the wait cannot starve them.
 template <class EV, int VPW = 16>
 __device__ __forceinline__ void surface_body(const Params& p, float* lds) {
     const int wave = wave_index();
-    const int lane = lane_id();
-    ModelPtr M = as_const(p.model);
-    EV ev(M, lds + wave * (p.slotsPerLane * 4 * 64) + lane);
+    EV ev(as_const(p.model), lds + wave * (p.slotsPerLane * 4 * 64) + lane_id());
     const uint32_t nWaves = gridDim.x * (blockDim.x >> 6);
     const uint32_t wave0 = blockIdx.x * (blockDim.x >> 6) + wave;
-    const float delta = 0.001f;
-    const float inv = -1.0f / delta;
     if (blockIdx.x < p.scanBlocks) {  // block-uniform
         scan_counts_block(p, blockIdx.x);
         __syncthreads();  // the block's offsets stores are in L2
@@ -2154,203 +2136,38 @@ __device__ __forceinline__ void surface_body(const Params& p, float* lds) {
             __hip_atomic_fetch_add(&p.ctr->scanDone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (blockIdx.x == 0) {  // k_finish's block-0 duties (finish_body), once every scan block is done:
-        // a look-back timeout of any scan block (error bit 0) is then in the counters it publishes
+    if (blockIdx.x == 0) {
         if (threadIdx.x < 64) surface_wait_scan(p);
         __syncthreads();
-        const uint32_t err = __hip_atomic_load(&p.ctr->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(p.ctr);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(p.hostCtr);
-        constexpr uint32_t kErrWord = __builtin_offsetof(DevCounters, error) / 4, kSurfWord = __builtin_offsetof(DevCounters, surfaceErr) / 4;
-        for (uint32_t i = threadIdx.x; i < sizeof(DevCounters) / 4; i += blockDim.x)
-            if (i != kSurfWord) dst[i] = i == kErrWord ? err : src[i];
-        __threadfence_system();
-        uint32_t* nx = reinterpret_cast<uint32_t*>(p.ctrNext);
-        const uint32_t nextEpoch = p.ctr->epoch + 1u;
-        constexpr uint32_t kEpochWord = __builtin_offsetof(DevCounters, epoch) / 4;
-        for (uint32_t i = threadIdx.x; i < sizeof(DevCounters) / 4; i += blockDim.x)
-            nx[i] = i == 0 ? 0x7fffffffu : (i == kEpochWord ? nextEpoch : 0u);
-        for (uint32_t i = threadIdx.x; i < kScanMaxBlocks; i += blockDim.x) p.scanStatusNext[i] = 0ull;
-        if (threadIdx.x < 64) {
-            const ShardCtr& sc = p.ctr->shard[threadIdx.x];
-            const uint32_t tv = wave_sum(sc.v), tt = wave_sum(sc.t), tp = wave_sum(sc.p), tb = wave_sum(sc.b),
-                           ts = wave_sum(sc.s);
-            if (threadIdx.x == 0) {
-                const uint32_t tot[7] = {p.mpuCount, tv, tt, tp + tb, ts, tp, (uint32_t)p.ctr->firstOverflow};
-                for (int i = 0; i < 7; ++i) p.totals[i] = tot[i];
-                if (err) atomicOr(&p.totals[7], err);  // raised, never stored: zeroed by k_precheck
-            }
-        }
+        publish_run<true>(p);
     }
     __shared__ uint32_t sCnt[2 * kShards];
     stage_shard_counts(p, 1, sCnt);            // ShardCtr::v
     stage_shard_counts(p, 2, sCnt + kShards);  // ShardCtr::t
     __syncthreads();
     bool scanSeen = blockIdx.x == 0;  // block 0 waited above
-if constexpr (VPW == 64) {
-    const ShardBatches sw(sCnt, p.vShardCap, 64);
-    for (uint32_t batch = wave0; batch < sw.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sw.locate(batch, &shard, &first, &count);
-        uint32_t rec = first + (uint32_t)lane;
-        const bool valid = rec < count;
-        if (!valid) rec = first;
-        const size_t ri = (size_t)shard * p.vShardCap + rec;
-        const VertexKey K = p.vk[ri];
-        const EdgeSeg E = edge_segment(p, K.w, K.vidKey >> 16);
-        // the root: the lane's 4 edge samples as one 4-point walk (vertex_body, 64 per wave)
-        float xs[4], ys[4], zs[4], fs[4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-            xs[s2] = edge_sample(E.e[0], E.d[0], s2);
-            ys[s2] = edge_sample(E.e[1], E.d[1], s2);
-            zs[s2] = edge_sample(E.e[2], E.d[2], s2);
-        }
-        CullMask cmv{0ull, 0ull};
-        if (p.cull) cmv = cull_mask_mpus(p, K.w);
-        if (p.debug & 256u) {  // ablation bit 8: no phase-A walk
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) fs[s2] = xs[s2];
-        } else {
-            ev.template evaln<0, false, 4>(xs, ys, zs, cmv, fs, nullptr);
-        }
-        const bool st0 = fs[0] >= 0.5f;
-        const int iv = ((fs[1] >= 0.5f) != st0) ? 1 : (((fs[2] >= 0.5f) != st0) ? 2 : 3);
-        const float fa = iv == 1 ? fs[0] : (iv == 2 ? fs[1] : fs[2]);
-        const float fb = iv == 1 ? fs[1] : (iv == 2 ? fs[2] : fs[3]);
-        const float scale = (0.5f - fa) / (fb - fa);
-        // value, colour and normal at the root (finish_body, 64 per wave)
-        float P[3];
-        vertex_root(E, (uint32_t)iv, scale, P);
-        const bool onSeg = scale >= 0.0f && scale <= 1.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f};
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (!(p.debug & 32u)) {  // ablation bit 5: no walks
-            CullMask cm{0ull, 0ull};
-            if (p.cull) {
-                if (ballot(!onSeg) == 0ull) cm = cmv;  // cull_mask_mpus(p, K.w), as just made
-                else cm = cull_mask_points(M, P[0], P[1], P[2], true, delta);
-            }
-            const float qx[4] = {P[0], P[0] + delta, P[0], P[0]};
-            const float qy[4] = {P[1], P[1], P[1] + delta, P[1]};
-            const float qz[4] = {P[2], P[2], P[2], P[2] + delta};
-            float g[4], c4[12];
-            ev.template evaln<1, true, 4>(qx, qy, qz, cm, g, c4);
-            c[0] = c4[0];
-            c[1] = c4[1];
-            c[2] = c4[2];
-            const float vtx = g[0];
-            nx = (g[1] - vtx) * inv;
-            ny = (g[2] - vtx) * inv;
-            nz = (g[3] - vtx) * inv;
-            const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
-            nx = nx * im;
-            ny = ny * im;
-            nz = nz * im;
-        }
-        if (!scanSeen) {
-            surface_wait_scan(p);
-            scanSeen = true;
-        }
-        const uint32_t gi = (uint32_t)surface_offs(p, K.w) + (K.vidKey & 0xffffu);
-        if (valid && gi < p.vCap) {  // past vCap: finish() grows and re-runs
-            p.pos[gi * 3 + 0] = P[0];
-            p.pos[gi * 3 + 1] = P[1];
-            p.pos[gi * 3 + 2] = P[2];
-            p.nrm[gi * 3 + 0] = nx;
-            p.nrm[gi * 3 + 1] = ny;
-            p.nrm[gi * 3 + 2] = nz;
-            p.col[gi * 3 + 0] = c[0];
-            p.col[gi * 3 + 1] = c[1];
-            p.col[gi * 3 + 2] = c[2];
-        }
-    }
-} else {
-    const ShardBatches sv(sCnt, p.vShardCap, 16);
-    const int qj = lane & 3;
+    const ShardBatches sv(sCnt, p.vShardCap, VPW);
     for (uint32_t batch = wave0; batch < sv.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sv.locate(batch, &shard, &first, &count);
-        uint32_t rec = first + (uint32_t)(lane >> 2);
-        const bool valid = rec < count;
-        if (!valid) rec = first;
-        const size_t ri = (size_t)shard * p.vShardCap + rec;
-        const VertexKey K = p.vk[ri];
+        const VertexSlot s = locate_vertex<VPW>(p, sv, batch);
+        const VertexKey K = p.vk[s.rec];
         const EdgeSeg E = edge_segment(p, K.w, K.vidKey >> 16);
-        // the root: lane j of the quad walks edge sample j (vertex_body, 16 per wave)
-        const float sx = edge_sample(E.e[0], E.d[0], qj);
-        const float sy = edge_sample(E.e[1], E.d[1], qj);
-        const float sz = edge_sample(E.e[2], E.d[2], qj);
-        CullMask cmv{0ull, 0ull};
-        if (p.cull) cmv = cull_mask_mpus(p, K.w);
-        float fv;
-        if (p.debug & 256u) fv = sx;  // ablation bit 8: no phase-A walk
-        else fv = ev.template eval<4, false>(sx, sy, sz, cmv, nullptr);
-        const float fs0 = quad_bcast<0>(fv), fs1 = quad_bcast<1>(fv), fs2 = quad_bcast<2>(fv), fs3 = quad_bcast<3>(fv);
-        const bool st0 = fs0 >= 0.5f;
-        const int iv = ((fs1 >= 0.5f) != st0) ? 1 : (((fs2 >= 0.5f) != st0) ? 2 : 3);
-        const float fa = iv == 1 ? fs0 : (iv == 2 ? fs1 : fs2);
-        const float fb = iv == 1 ? fs1 : (iv == 2 ? fs2 : fs3);
-        const float scale = (0.5f - fa) / (fb - fa);
-        // value, colour and normal at the root (finish_body, 16 per wave)
+        const CullMask cmv = edge_mask(p, K.w);
+        const VertexPos R = root_bracket<EV, VPW>(ev, p, E, cmv, s);
         float P[3];
-        vertex_root(E, (uint32_t)iv, scale, P);
-        const bool onSeg = scale >= 0.0f && scale <= 1.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f};
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (!(p.debug & 32u)) {  // ablation bit 5: no walks
-            CullMask cm{0ull, 0ull};
-            if (p.cull) {
-                if (ballot(!onSeg) == 0ull) cm = cmv;  // cull_mask_mpus(p, K.w), as just made
-                else cm = cull_mask_points(M, P[0], P[1], P[2], true, delta);
-            }
-            const float qx = qj == 1 ? P[0] + delta : P[0];
-            const float qy = qj == 2 ? P[1] + delta : P[1];
-            const float qz = qj == 3 ? P[2] + delta : P[2];
-            float c4[3];
-            const float g = ev.template eval<1, true>(qx, qy, qz, cm, c4);
-            c[0] = quad_bcast<0>(c4[0]);
-            c[1] = quad_bcast<0>(c4[1]);
-            c[2] = quad_bcast<0>(c4[2]);
-            const float vtx = quad_bcast<0>(g);
-            nx = (quad_bcast<1>(g) - vtx) * inv;
-            ny = (quad_bcast<2>(g) - vtx) * inv;
-            nz = (quad_bcast<3>(g) - vtx) * inv;
-            const float im = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
-            nx = nx * im;
-            ny = ny * im;
-            nz = nz * im;
-        }
+        vertex_root(E, R.iv, R.scale, P);
+        const Shaded S =
+            shade_vertex<EV, VPW>(ev, p, P, R.scale >= 0.0f && R.scale <= 1.0f, s, [&] { return cmv; });
         if (!scanSeen) {
             surface_wait_scan(p);
             scanSeen = true;
         }
-        const uint32_t gi = (uint32_t)surface_offs(p, K.w) + (K.vidKey & 0xffffu);
-        if (valid && qj < 3 && gi < p.vCap) {  // past vCap: finish() grows and re-runs
-            const uint32_t o = gi * 3 + (uint32_t)qj;
-            p.pos[o] = qj == 0 ? P[0] : (qj == 1 ? P[1] : P[2]);
-            p.nrm[o] = qj == 0 ? nx : (qj == 1 ? ny : nz);
-            p.col[o] = qj == 0 ? c[0] : (qj == 1 ? c[1] : c[2]);
-        }
+        const uint32_t gi = (uint32_t)offs_word<true>(p, K.w) + (K.vidKey & 0xffffu);
+        store_vertex<VPW>(p, s, gi, P, S);
     }
-}
     if (p.debug & 64u) return;  // ablation bit 6: no triangles
-    const ShardBatches sb(sCnt + kShards, p.tShardCap, 64);
-    if (wave0 < sb.total && !scanSeen) surface_wait_scan(p);
-    for (uint32_t batch = wave0; batch < sb.total; batch += nWaves) {
-        uint32_t shard, first, count;
-        sb.locate(batch, &shard, &first, &count);
-        const uint32_t t = first + lane;
-        if (t >= count) continue;
-        const TriRec R = p.tq[(size_t)shard * p.tShardCap + t];
-        const uint64_t o = surface_offs(p, ((R.a >> 12) << 6) | shard);  // the record's shard is w & 63
-        const uint32_t gt = (uint32_t)(o >> 32) + (R.a & 2047u);
-        const uint32_t base = (uint32_t)o;
-        if (gt >= p.tCap) continue;  // finish() grows and re-runs
-        p.tris[gt * 3 + 0] = base + (R.b & 2047u);
-        p.tris[gt * 3 + 1] = base + ((R.b >> 11) & 2047u);
-        p.tris[gt * 3 + 2] = base + ((R.b >> 22) | (((R.a >> 11) & 1u) << 10));
-    }
+    const ShardBatches st(sCnt + kShards, p.tShardCap, 64);
+    if (wave0 < st.total && !scanSeen) surface_wait_scan(p);
+    triangle_pass<true>(p, st, wave0, nWaves);
 }
 
 // Field probe for tests: mode 0 quads of consecutive points, 1 per point, 2 + colour.

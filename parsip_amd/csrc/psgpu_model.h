@@ -56,7 +56,7 @@ namespace psgpu {
 //                                                                  (edge_segment, edge_sample)
 //   roots            fl(a + fl(scale fl(b - a))), a, b two edge samples, scale in [0, 1]: k_finish
 //                    takes the MPU masks only when every vertex of the wave is on its segment
-//   normal points    fl(root + 0.001f)                                           (finish_body)
+//   normal points    fl(root + 0.001f)                                          (shade_vertex)
 // In exact arithmetic the first three lie in [o, o + 7 cs] and the last within 0.001f <
 // 0.0010001 of it.  Every fl() above rounds a value of magnitude <= M + 0.0011 (or a product
 // below it), so it moves the result by at most u (M + 0.0011); a coordinate depends on at most

@@ -105,6 +105,23 @@ def test_interpreter_matches_oracle(poly, oracle, name):
         assert not poly.jit_active
 
 
+@pytest.mark.parametrize("fquad", [0, 1, 3])
+def test_interpreter_off_segment_roots_every_finish_layout(poly, oracle, fquad):
+    """Roots off their bracketing segments (randlines31: the bracket hits fb == fa, NaN positions)
+    through k_finish itself, 64 / 16 / 32 vertices per wave: a wave that holds one takes the
+    culling mask of its own points' box instead of its MPUs' masks."""
+    name = "randlines%d" % du.NAN_SEED
+    assert not np.isfinite(du.oracle_mesh(oracle, name).pos).all(), "no off-segment root in the oracle's mesh"
+    opts = {gpu.OPT_FUSED_SURFACE: 0, gpu.OPT_FINISH_QUAD: fquad}
+    try:
+        set_options(poly, opts)
+        with interpreter(poly):
+            run_and_compare(poly, oracle, name, never=F, tag=f"interp finish_quad {fquad}")
+            assert not poly.jit_active
+    finally:
+        set_options(poly, {k: DEFAULTS[k] for k in opts})
+
+
 def test_checker_generated_kernels(poly, oracle):
     """V = 1,344 / T = 1,372 through the structure-specialised kernels of the 60-primitive tree."""
     t0 = time.perf_counter()

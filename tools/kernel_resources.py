@@ -12,7 +12,7 @@ tree-split k_mpu (2 MPUs per block); the others take none.
 Static instruction mix per kernel from llvm-objdump (VALU = v_* except v_readlane /
 v_readfirstlane / v_writelane counted as VALU too; s_nop; s_waitcnt; packed fp32).
 
-Usage: python tools/kernel_resources.py [--configs C3,C5] [--out profiles/r05_kernel_resources.json]
+Usage: python tools/kernel_resources.py --out FILE.json [--configs C3,C5]
        [--variant name=ENV=VALUE[;ENV=VALUE]] ...
 """
 import argparse
@@ -34,7 +34,10 @@ ROLE = {"jit_precheck": "k_precheck", "jit_mpu": "k_mpu", "jit_vertex": "k_verte
         "jit_vertex_w": "k_vertex (wide, 64/wave)", "jit_finish": "k_finish (64/wave)",
         "jit_finish_q": "k_finish (quad, 16/wave)", "jit_finish_p": "k_finish (pair, 32/wave)",
         "jit_precheck_s": "k_precheck (tree split)", "jit_mpu_s": "k_mpu (tree split)",
-        "jit_surface": "k_vertex + k_finish in one launch (small launches, quad layouts)", "jit_probe": "probe"}
+        "jit_surface": "k_vertex + k_finish in one launch (small launches, quad layouts)",
+        "jit_surface_w": "k_vertex + k_finish in one launch (wide layouts, 64/wave)",
+        "jit_front": "k_precheck + k_mpu in one launch (small launches)",
+        "jit_front_s": "k_precheck + k_mpu in one launch (tree split)", "jit_probe": "probe"}
 
 
 def parse_metadata(co: str) -> dict:
@@ -141,7 +144,7 @@ def compile_variant(config: str, mode: int, env: dict) -> dict:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C3,C5")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_kernel_resources.json"))
+    ap.add_argument("--out", required=True, help="the JSON to write (profiles/ holds the committed records)")
     ap.add_argument("--variant", action="append", default=[],
                     help="name=ENV=VALUE[;ENV=VALUE]: an extra structure-tier compile with that environment")
     a = ap.parse_args()
