@@ -524,6 +524,32 @@ int  psgpu_group_download_mesh(psgpu_group* g, float* pos, float* nrm, float* co
                                uint64_t* mpuOffsets);
 /* The whole mesh in HBM of part dstPart's device (peer copies over xGMI + rebase). */
 int  psgpu_group_gather(psgpu_group* g, int dstPart, PsMeshDevice* out);
+/* The group's run welded into one watertight indexed mesh in HBM of part dstPart's device:
+ * psgpu_weld's contract (above) over the group's global index space, where input vertex
+ * gi = vertexBase[p] + mpuOffsets_p[w] + vid of part p sits on the edge of MPU w + mpuBegin_p.
+ * The seams between parts close: the result equals, byte for byte, psgpu_weld of one
+ * context's run over the whole range, for any number of parts and any split.  Blocking; a
+ * pending run is collected first (psgpu_group_finish) and the mesh is gathered on dstPart's
+ * device (the pointers of an earlier psgpu_group_gather are overwritten).
+ * PSGPU_RET_PARAM_ERROR when there is no group run, dstPart is out of range, a part reported
+ * an overflow MPU, a lattice axis has 2^20 / 7 MPUs or more, or a part's own run has been
+ * superseded since the group's finish (a call through psgpu_group_context's pointer).  An
+ * empty mesh welds to an empty mesh.  The buffers are allocated by the group's first weld,
+ * grown on demand and freed by psgpu_group_destroy or a change of dstPart: a group that never
+ * welds pays nothing.  Ranks in separate processes (psgpu_comm_*) and the compat mode
+ * (parsip_gpu_gui.h) have no weld across their parts. */
+int  psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info);
+/* The welded mesh in HBM / on the host (any pointer may be NULL): PSGPU_RET_PARAM_ERROR unless
+ * the group's current run has been welded; psgpu_group_set_model, psgpu_group_polygonize,
+ * psgpu_group_set_split and psgpu_group_set_option(PSGPU_OPT_CAPACITY) invalidate a weld. */
+int  psgpu_group_weld_device(psgpu_group* g, PsWeldDevice* out);
+int  psgpu_group_download_weld(psgpu_group* g, float* pos, float* nrm, float* col, uint32_t* tris,
+                               uint32_t* vertexMap);
+/* hipEvent times (ms) of the last psgpu_group_weld with PSGPU_OPT_KERNEL_TIMING set on the
+ * group, on the gathering device's stream: the whole weld, the gather, the parts' edge ids
+ * and their copies (as far as they outlast the gather), the mark, then resolve, scan, emit
+ * and map; returns the count filled. */
+int  psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char** names);
 int  psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCtMPUs);
 /* Blocking drop-in for PS::SIMDPOLY::Polygonize over every device of the group. */
 int  psgpu_group_polygonize_mpus(psgpu_group* g, float cellsize, const PsSoaBlobPrims* prims,

@@ -173,6 +173,23 @@ inline int Polygonize(float cellsize, const Prims& prims, const Mats& mats, cons
                               reinterpret_cast<PsMpuProcessStats*>(lpProcessStats), ctx);
 }
 
+/* A finished run's mesh welded by lattice-edge identity (psgpu_weld, psgpu_group_weld: one
+ * vertex per lattice edge, watertight across MPU seams), its counts and host copies. */
+struct Welded {
+    PsWeldInfo info{};
+    std::vector<float> pos, nrm, col;  /* info.ctVertices * 3 each */
+    std::vector<uint32_t> tris;        /* info.ctTriangles * 3, welded ids */
+    std::vector<uint32_t> vertexMap;   /* info.ctInputVertices */
+    void resize(const PsWeldInfo& i) {
+        info = i;
+        pos.resize(size_t(i.ctVertices) * 3);
+        nrm.resize(size_t(i.ctVertices) * 3);
+        col.resize(size_t(i.ctVertices) * 3);
+        tris.resize(size_t(i.ctTriangles) * 3);
+        vertexMap.resize(i.ctInputVertices);
+    }
+};
+
 /* SimdPoly-shaped adapter (PS_HighPerformanceRender.h:15-33) over a device-resident
  * compact mesh: setModel once per edit, run() per frame, mesh() for GL / export. */
 template <class Prims, class Mats, class Ops>
@@ -192,15 +209,9 @@ public:
     }
     int finish(PsMeshInfo* info) { return psgpu_finish(ctx_.get(), info); }
     int mesh(PsMeshDevice* out) { return psgpu_mesh_device(ctx_.get(), out); }
-    /* The finished run's mesh welded by lattice-edge identity (psgpu_weld: one vertex per
-     * lattice edge, watertight across MPU seams), its counts and host copies. */
-    struct Welded {
-        PsWeldInfo info{};
-        std::vector<float> pos, nrm, col;  /* info.ctVertices * 3 each */
-        std::vector<uint32_t> tris;        /* info.ctTriangles * 3, welded ids */
-        std::vector<uint32_t> vertexMap;   /* info.ctInputVertices */
-    };
-    /* After finish(); PSGPU_RET_PARAM_ERROR without a finished run (out is left empty). */
+    /* The finished run's mesh welded (psgpu_weld).  After finish(); PSGPU_RET_PARAM_ERROR
+     * without a finished run (out is left empty). */
+    using Welded = psgpu::Welded;
     int weld(Welded* out) {
         if (!ctx_.ok()) return ctx_.status();
         if (!out) return PSGPU_RET_PARAM_ERROR;
@@ -208,12 +219,7 @@ public:
         PsWeldInfo info;
         const int rc = psgpu_weld(ctx_.get(), &info);
         if (rc != PSGPU_RET_SUCCESS) return rc;
-        out->info = info;
-        out->pos.resize(size_t(info.ctVertices) * 3);
-        out->nrm.resize(size_t(info.ctVertices) * 3);
-        out->col.resize(size_t(info.ctVertices) * 3);
-        out->tris.resize(size_t(info.ctTriangles) * 3);
-        out->vertexMap.resize(info.ctInputVertices);
+        out->resize(info);
         return psgpu_download_weld(ctx_.get(), out->pos.data(), out->nrm.data(), out->col.data(), out->tris.data(),
                                    out->vertexMap.data());
     }
@@ -333,6 +339,22 @@ public:
 
     /* the whole mesh in HBM of the device (the parts gathered, vertex ids rebased) */
     int mesh(PsMeshDevice* out) { return psgpu_group_gather(grp_.get(), 0, out); }
+    /* The run's mesh welded into one watertight indexed mesh, the seams between the parts
+     * included (psgpu_group_weld on part 0's device): the same bytes as one context's weld of
+     * the whole lattice.  After run(); PSGPU_RET_PARAM_ERROR without a run (out is left empty). */
+    int weld(Welded* out) {
+        if (!grp_.ok()) return grp_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Welded();
+        PsWeldInfo info;
+        const int rc = psgpu_group_weld(grp_.get(), 0, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_group_download_weld(grp_.get(), out->pos.data(), out->nrm.data(), out->col.data(),
+                                         out->tris.data(), out->vertexMap.data());
+    }
+    /* The same weld left in HBM (valid until the next weld). */
+    int weldDevice(PsWeldDevice* out) { return psgpu_group_weld_device(grp_.get(), out); }
     const PsMeshInfo& info() const { return info_; }
     const PsSoaBlobPrims& prims() const { return prims_; }
     const PsSoaBlobOps& ops() const { return ops_; }

@@ -9,7 +9,9 @@
 //                   run), launched on every device's stream at once; the count exchange is
 //                   a host read of each part's totals; psgpu_group_gather assembles the
 //                   parts on one device with peer copies over xGMI (hipMemcpyPeerAsync) and
-//                   a rebase kernel, or psgpu_group_download_mesh to the host.
+//                   a rebase kernel, or psgpu_group_download_mesh to the host;
+//                   psgpu_group_weld welds the gathered parts into one watertight mesh
+//                   there (the kernels: psgpu_weld.hip).
 //   psgpu_comm_*    one process per GPU (torchrun / MPI launchers): each rank owns a range
 //                   of the same split (computed identically on every rank) and the parts'
 //                   totals are exchanged with one RCCL all-gather of 8 words per rank on
@@ -32,6 +34,13 @@
 #include "psgpu_launch.h"
 
 using namespace psgpu;
+
+namespace {
+constexpr int kGroupWeldPhases = 8;  // psgpu_group_weld_times
+const char* kGroupWeldPhaseNames[kGroupWeldPhases] = {
+    "group weld total", "gather", "k_weld_edges + copies", "table fill + k_weld_mark_ids",
+    "k_weld_resolve",   "k_weld_scan", "k_weld_emit", "k_weld_map"};
+}  // namespace
 
 struct psgpu_group {
     std::vector<psgpu_ctx*> parts;
@@ -56,6 +65,21 @@ struct psgpu_group {
     // one rank's parts summed for the RCCL exchange (psgpu_comm_exchange_group)
     std::vector<hipEvent_t> done;
     uint32_t* sumTotals = nullptr;
+    // psgpu_group_weld: runSeq counts whatever supersedes the group's run or its split
+    // (set_model, polygonize, set_split, a capacity change), as psgpu_ctx::runSeq does for a
+    // context; partSeq is each part's own runSeq when the group's finish collected it
+    uint64_t runSeq = 0;
+    std::vector<uint64_t> partSeq;
+    // the welded mesh on one part's device: allocated by the first weld, grown on demand
+    int weldPart = -1;
+    WeldState weld;                    // doneSeq: the group's runSeq of the welded run
+    uint64_t* gEdge = nullptr;         // the gathered vertices' edge ids, beside the gathered mesh
+    size_t capEdge = 0;
+    std::vector<uint64_t*> partEdge;   // each part's edge ids on its own device (k_weld_edges)
+    std::vector<size_t> partEdgeCap;
+    std::vector<hipEvent_t> partEdgeEv;  // ... and the event the gather stream waits for
+    hipEvent_t weldEv[kGroupWeldPhases] = {};
+    float weldMs[kGroupWeldPhases] = {};
 };
 
 namespace {
@@ -74,6 +98,31 @@ void free_gather(psgpu_group* g) {
     g->gatherStream = nullptr;
     g->gCapV = g->gCapT = g->gCapM = 0;
     g->gatherPart = -1;
+}
+
+void free_weld(psgpu_group* g) {
+    if (g->weldPart >= 0) {
+        (void)hipSetDevice(g->parts[g->weldPart]->device);
+        weld_state_free(g->weld);  // (hipFree waits for the device)
+        if (g->gEdge) (void)hipFree(g->gEdge);
+        for (hipEvent_t& e : g->weldEv) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    for (size_t p = 0; p < g->partEdge.size(); ++p) {
+        if (!g->partEdge[p] && !g->partEdgeEv[p]) continue;
+        (void)hipSetDevice(g->parts[p]->device);
+        if (g->partEdge[p]) (void)hipFree(g->partEdge[p]);
+        if (g->partEdgeEv[p]) (void)hipEventDestroy(g->partEdgeEv[p]);
+    }
+    g->partEdge.clear();
+    g->partEdgeCap.clear();
+    g->partEdgeEv.clear();
+    g->weld = WeldState{};
+    g->gEdge = nullptr;
+    g->capEdge = 0;
+    g->weldPart = -1;
 }
 
 uint32_t lattice_total(psgpu_group* g, float cs) {
@@ -201,6 +250,7 @@ int psgpu_group_create(const int* devices, int nParts, psgpu_group** out) {
 
 void psgpu_group_destroy(psgpu_group* g) {
     if (!g) return;
+    free_weld(g);
     free_gather(g);
     if (!g->parts.empty()) (void)hipSetDevice(g->parts[0]->device);
     for (hipEvent_t e : g->done)
@@ -231,6 +281,7 @@ int psgpu_group_set_option(psgpu_group* g, int option, int64_t value) {
         g->bounds.clear();  // re-split at the next polygonize
         return PSGPU_RET_SUCCESS;
     }
+    if (option == PSGPU_OPT_CAPACITY) ++g->runSeq;  // the parts drop their runs
     for (psgpu_ctx* c : g->parts) {
         const int rc = psgpu_set_option(c, option, value);
         if (rc != PSGPU_RET_SUCCESS) return rc;
@@ -241,6 +292,7 @@ int psgpu_group_set_option(psgpu_group* g, int option, int64_t value) {
 int psgpu_group_set_model(psgpu_group* g, const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* mats,
                           const PsSoaBlobOps* ops) {
     if (!g) return PSGPU_RET_PARAM_ERROR;
+    ++g->runSeq;
     // one hiprtc job serves every part (jit_request dedups by source); each device loads it
     for (psgpu_ctx* c : g->parts) {
         const int rc = psgpu_set_model(c, prims, mats, ops);
@@ -265,6 +317,7 @@ int psgpu_group_set_split(psgpu_group* g, const uint32_t* bounds) {
     g->bounds.assign(bounds, bounds + n + 1);
     g->balance = PSGPU_GROUP_BALANCE_FIXED;
     g->planned = false;
+    ++g->runSeq;
     return PSGPU_RET_SUCCESS;
 }
 
@@ -276,6 +329,7 @@ int psgpu_group_get_split(psgpu_group* g, uint32_t* bounds) {
 
 int psgpu_group_polygonize(psgpu_group* g, float cellsize) {
     if (!g || !g->parts[0]->haveModel || !(cellsize > 0.0f)) return PSGPU_RET_PARAM_ERROR;
+    ++g->runSeq;
     const uint32_t total = lattice_total(g, cellsize);
     const size_t n = g->parts.size();
     const bool replan = g->balance == PSGPU_GROUP_BALANCE_PLAN &&
@@ -311,9 +365,11 @@ int psgpu_group_finish(psgpu_group* g, PsMeshInfo* totalOut, PsGroupPart* partsO
     if (g->pending) {
         g->pending = false;
         g->info.assign(n, PsMeshInfo{});
+        g->partSeq.assign(n, ~0ull);
         for (size_t p = 0; p < n; ++p) {
             const int rc = psgpu_finish(g->parts[p], &g->info[p]);
             if (rc != PSGPU_RET_SUCCESS) return rc;
+            g->partSeq[p] = g->parts[p]->runSeq;
         }
         // the count exchange: each part's place in the global index space
         g->vBase.assign(n, 0);
@@ -390,18 +446,16 @@ int psgpu_group_download_mesh(psgpu_group* g, float* pos, float* nrm, float* col
     return PSGPU_RET_SUCCESS;
 }
 
-// The whole mesh in HBM of one part's device: peer copies of every part (xGMI), then the
-// rebase kernel per part.  The returned pointers stay valid until the next gather.
-int psgpu_group_gather(psgpu_group* g, int dstPart, PsMeshDevice* out) {
-    if (!g || !out || dstPart < 0 || dstPart >= (int)g->parts.size()) return PSGPU_RET_PARAM_ERROR;
-    PsMeshInfo T;
-    int rc = psgpu_group_finish(g, &T, nullptr);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
+// The gather of the finished run (totals T) enqueued on the gather stream of dstPart's device,
+// which it leaves current; `before` (or null): an event recorded on that stream first.
+static int gather_enqueue(psgpu_group* g, int dstPart, const PsMeshInfo& T, hipEvent_t before) {
+    int rc;
     if (g->gatherPart != dstPart) free_gather(g);
     psgpu_ctx* dst = g->parts[dstPart];
     PSGPU_CHECK(hipSetDevice(dst->device));
     if (!g->gatherStream) PSGPU_CHECK(hipStreamCreateWithFlags(&g->gatherStream, hipStreamNonBlocking));
     g->gatherPart = dstPart;
+    if (before) PSGPU_CHECK(hipEventRecord(before, g->gatherStream));
     const size_t V = std::max<size_t>(T.ctVertices, 1), Tn = std::max<size_t>(T.ctTriangles, 1),
                  M = (size_t)T.ctMPUs + 1;
     auto grow = [](auto*& ptr, size_t& cap, size_t need, size_t elt) -> hipError_t {
@@ -443,13 +497,158 @@ int psgpu_group_gather(psgpu_group* g, int dstPart, PsMeshDevice* out) {
         mBase += I.ctMPUs;
     }
     if (mBase == 0) PSGPU_CHECK(hipMemsetAsync(g->gOffs, 0, 8, s));
-    PSGPU_CHECK(hipStreamSynchronize(s));
+    return PSGPU_RET_SUCCESS;
+}
+
+// The whole mesh in HBM of one part's device: peer copies of every part (xGMI), then the
+// rebase kernel per part.  The returned pointers stay valid until the next gather.
+int psgpu_group_gather(psgpu_group* g, int dstPart, PsMeshDevice* out) {
+    if (!g || !out || dstPart < 0 || dstPart >= (int)g->parts.size()) return PSGPU_RET_PARAM_ERROR;
+    PsMeshInfo T;
+    int rc = psgpu_group_finish(g, &T, nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    rc = gather_enqueue(g, dstPart, T, nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    PSGPU_CHECK(hipStreamSynchronize(g->gatherStream));
     out->pos = g->gPos;
     out->nrm = g->gNrm;
     out->col = g->gCol;
     out->tris = g->gTris;
     out->mpuOffsets = g->gOffs;
     return PSGPU_RET_SUCCESS;
+}
+
+// The group's run welded as one mesh on dstPart's device (psgpu_weld's contract over the
+// gathered index space): every part turns its vertex records into edge ids on its own device
+// and stream (k_weld_edges), the gather stream gathers the mesh, waits for each part's event
+// and copies its ids behind the previous part's, then marks from the ids and runs the
+// context weld's resolve / scan / emit / map on the gathered arrays.
+int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
+    if (!g || dstPart < 0 || dstPart >= (int)g->parts.size()) return PSGPU_RET_PARAM_ERROR;
+    PsMeshInfo T;
+    int rc = psgpu_group_finish(g, &T, nullptr);  // PSGPU_RET_PARAM_ERROR without a run
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    if (T.firstOverflowMPU >= 0) return PSGPU_RET_PARAM_ERROR;  // past the reference's 512 per MPU
+    const size_t n = g->parts.size();
+    for (size_t p = 0; p < n; ++p) {
+        const psgpu_ctx* c = g->parts[p];
+        // the part still holds the run the group collected (not one made through its own pointer)
+        if (!weld_run_ready(c) || c->runSeq != g->partSeq[p]) return PSGPU_RET_PARAM_ERROR;
+        for (int a = 0; a < 3; ++a)
+            if (7ull * c->dims[a] >= (1ull << 20)) return PSGPU_RET_PARAM_ERROR;  // 20 bits a coordinate
+    }
+    if (g->weldPart != dstPart) free_weld(g);
+    g->weldPart = dstPart;
+    WeldState& W = g->weld;
+    W.doneSeq = ~0ull;
+    memset(&W.info, 0, sizeof(W.info));
+    W.info.ctInputVertices = T.ctVertices;
+    W.info.ctTriangles = T.ctTriangles;
+    for (float& ms : g->weldMs) ms = 0.0f;
+    if (T.ctVertices == 0) {  // nothing to launch: an empty mesh welds to an empty mesh
+        W.doneSeq = g->runSeq;
+        if (info) *info = W.info;
+        return PSGPU_RET_SUCCESS;
+    }
+    if (g->partEdge.size() != n) {
+        g->partEdge.assign(n, nullptr);
+        g->partEdgeCap.assign(n, 0);
+        g->partEdgeEv.assign(n, nullptr);
+    }
+    auto grow = [](uint64_t*& ptr, size_t& cap, size_t need) -> hipError_t {
+        if (need <= cap && ptr) return hipSuccess;
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        const size_t m = std::max(need, cap + cap / 2);
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), m * sizeof(uint64_t));
+        cap = e == hipSuccess ? m : 0;
+        return e;
+    };
+    // the parts' edge ids, each on its own device and stream: devices work side by side
+    for (size_t p = 0; p < n; ++p) {
+        psgpu_ctx* c = g->parts[p];
+        if (!g->info[p].ctVertices) continue;
+        rc = set_device(c);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        PSGPU_CHECK(grow(g->partEdge[p], g->partEdgeCap[p], g->info[p].ctVertices));
+        if (!g->partEdgeEv[p]) PSGPU_CHECK(hipEventCreateWithFlags(&g->partEdgeEv[p], hipEventDisableTiming));
+        rc = weld_edges(c, g->partEdge[p], c->stream);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        PSGPU_CHECK(hipEventRecord(g->partEdgeEv[p], c->stream));
+    }
+    psgpu_ctx* dst = g->parts[dstPart];
+    PSGPU_CHECK(hipSetDevice(dst->device));
+    const bool timed = dst->timing != 0;
+    if (timed)
+        for (hipEvent_t& e : g->weldEv)
+            if (!e) PSGPU_CHECK(hipEventCreate(&e));
+    PSGPU_CHECK(grow(g->gEdge, g->capEdge, T.ctVertices));
+    rc = gather_enqueue(g, dstPart, T, timed ? g->weldEv[0] : nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    hipStream_t s = g->gatherStream;
+    if (timed) PSGPU_CHECK(hipEventRecord(g->weldEv[1], s));
+    for (size_t p = 0; p < n; ++p) {
+        if (!g->info[p].ctVertices) continue;
+        PSGPU_CHECK(hipStreamWaitEvent(s, g->partEdgeEv[p], 0));
+        PSGPU_CHECK(hipMemcpyPeerAsync(g->gEdge + g->vBase[p], dst->device, g->partEdge[p], g->parts[p]->device,
+                                       (size_t)g->info[p].ctVertices * sizeof(uint64_t), s));
+    }
+    if (timed) PSGPU_CHECK(hipEventRecord(g->weldEv[2], s));
+    WeldGathered in{g->gPos, g->gNrm, g->gCol, g->gTris, g->gEdge, T.ctVertices, T.ctTriangles};
+    uint64_t totals = 0;
+    rc = weld_gathered(W, in, s, timed ? g->weldEv + 3 : nullptr, &totals);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    PSGPU_CHECK(hipStreamSynchronize(s));
+    if (timed) {
+        (void)hipEventElapsedTime(&g->weldMs[0], g->weldEv[0], g->weldEv[kGroupWeldPhases - 1]);
+        for (int k = 1; k < kGroupWeldPhases; ++k)
+            (void)hipEventElapsedTime(&g->weldMs[k], g->weldEv[k - 1], g->weldEv[k]);
+    }
+    W.info.ctVertices = (uint32_t)totals;
+    W.info.ctSeamVertices = (uint32_t)(totals >> 32);
+    W.doneSeq = g->runSeq;
+    if (info) *info = W.info;
+    return PSGPU_RET_SUCCESS;
+}
+
+// the group's current run has been welded
+static bool group_welded(const psgpu_group* g) {
+    return g && g->haveResult && !g->pending && g->weldPart >= 0 && g->weld.doneSeq == g->runSeq;
+}
+
+int psgpu_group_weld_device(psgpu_group* g, PsWeldDevice* out) {
+    if (!out || !group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    const WeldState& W = g->weld;
+    out->pos = W.pos;
+    out->nrm = W.nrm;
+    out->col = W.col;
+    out->tris = W.tris;
+    out->vertexMap = W.map;
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_group_download_weld(psgpu_group* g, float* pos, float* nrm, float* col, uint32_t* tris,
+                              uint32_t* vertexMap) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    PSGPU_CHECK(hipSetDevice(g->parts[g->weldPart]->device));
+    const WeldState& W = g->weld;
+    const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
+    if (pos && V) PSGPU_CHECK(hipMemcpy(pos, W.pos, V * 12, hipMemcpyDeviceToHost));
+    if (nrm && V) PSGPU_CHECK(hipMemcpy(nrm, W.nrm, V * 12, hipMemcpyDeviceToHost));
+    if (col && V) PSGPU_CHECK(hipMemcpy(col, W.col, V * 12, hipMemcpyDeviceToHost));
+    if (tris && T) PSGPU_CHECK(hipMemcpy(tris, W.tris, T * 12, hipMemcpyDeviceToHost));
+    if (vertexMap && Vin) PSGPU_CHECK(hipMemcpy(vertexMap, W.map, Vin * 4, hipMemcpyDeviceToHost));
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
+    if (!g) return 0;
+    const int n = std::min(maxPhases, kGroupWeldPhases);
+    for (int k = 0; k < n; ++k) {
+        if (ms) ms[k] = g->weldMs[k];
+        if (names) names[k] = kGroupWeldPhaseNames[k];
+    }
+    return n;
 }
 
 int psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCt) {

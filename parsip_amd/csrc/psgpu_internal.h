@@ -25,7 +25,8 @@ constexpr int kExportPieces = 16;  // at most, in the blocking export (psgpu_hos
 constexpr size_t kExportPieceBytes = 1u << 20;  // its target piece size
 
 // The device weld of a finished run (psgpu_weld.hip): its own buffers, allocated on the first
-// psgpu_weld of the context, grown on demand, freed by psgpu_destroy (weld_free).
+// psgpu_weld of the context, grown on demand, freed by psgpu_destroy (weld_free).  A group
+// keeps one of its own for psgpu_group_weld, on the gathering part's device (psgpu_group.cpp).
 constexpr int kWeldPhases = 6;  // psgpu_weld_times: the whole weld, then its five launches
 struct WeldState {
     unsigned char* table = nullptr;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
@@ -179,6 +180,26 @@ int hip_fail(hipError_t e, const char* what);
 int set_device(psgpu_ctx* c);
 // Free the weld's buffers and events (psgpu_weld.hip); the context's device is current.
 void weld_free(psgpu_ctx* c);
+// The same for a weld state that no context owns (a group's, psgpu_group.cpp); its device is current.
+void weld_state_free(WeldState& W);
+// The context's run is finished, superseded by nothing newer, and whole: it can be welded.
+bool weld_run_ready(const psgpu_ctx* c);
+// A group's weld (psgpu_group_weld), host wrappers of the kernels in psgpu_weld.hip.
+// weld_edges: the edge id of every vertex of the context's finished run (all ones: not on an
+// MPU face) into edge[0 .. ctVertices) on the context's device, enqueued on s; the context's
+// device is current.
+int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s);
+// weld_gathered: the weld of a gathered mesh of V > 0 vertices whose edge ids are edge[0 .. V),
+// into W's buffers (grown here), enqueued on s of the current device.  ev (null: untimed): five
+// events, one recorded after each launch (mark, resolve, scan, emit, map).  *totals (welded |
+// seam << 32) is written by a copy on s: read it after s has been waited for.
+struct WeldGathered {
+    const float *pos, *nrm, *col;
+    const uint32_t* tris;
+    const uint64_t* edge;
+    uint32_t V, T;
+};
+int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals);
 // The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.

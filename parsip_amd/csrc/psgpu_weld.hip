@@ -20,6 +20,16 @@
 //                   their pos / nrm / col staged through LDS (16-byte loads, coalesced stores)
 //   k_weld_map      vertexMap[gi] = id[rep[gi]] and tris = id[rep[tris]], 16 bytes a lane
 //
+// A group's parts (psgpu_group_weld, psgpu_group.cpp) weld in the gathered mesh's global index
+// space.  The gather brings no records, so each part names its vertices' edges itself:
+//
+//   k_weld_edges    on the part's device, one lane per vertex record: edge[gi] = the 62-bit
+//                   edge id k_weld_mark composes (all ones: interior); the arrays are copied
+//                   behind one another on the gathering device
+//   k_weld_mark_ids there, one lane per gathered vertex: k_weld_mark's table insert from the id
+//
+// and k_weld_resolve .. k_weld_map run on the gathered arrays as they do on a context's.
+//
 // The phases are ordered by kernel boundaries alone: no block waits for another inside a
 // launch.  Every value written is a function of the records alone (the table's slot
 // assignment depends on arrival order, the minimum in a slot does not), so two welds of one
@@ -111,6 +121,75 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_mark(WeldParams q) {
     uint32_t slot = weld_hash(id) & q.tableMask;
     // at most half the slots are ever taken (psgpu_weld sizes the table), so an empty or
     // matching slot comes up; the bound only keeps a corrupt record from spinning
+    for (uint32_t tries = 0; tries <= q.tableMask; ++tries) {
+        const uint64_t seen = atomicCAS((unsigned long long*)&q.keys[slot], (unsigned long long)kEmptyKey,
+                                        (unsigned long long)id);
+        if (seen == kEmptyKey || seen == id) {
+            atomicMin(&q.mins[slot], gi);
+            q.rep[gi] = slot;
+            return;
+        }
+        slot = (slot + 1u) & q.tableMask;
+    }
+    q.rep[gi] = kNoSlot;
+}
+
+// A part's records as edge ids (psgpu_group_weld): k_weld_mark's shard lookup, seam test and
+// id, written to edge[gi] (gi local to the part) instead of entering a table; the array was
+// filled with ones, so an interior record and a missing one both read as kEmptyKey.
+struct WeldEdgeParams {
+    const VertexKey* vk;
+    const uint64_t* offs;
+    uint32_t vShardCap;
+    uint32_t shardV[kShards];
+    uint32_t dims[3];
+    uint32_t mpuBegin, mpuCount;
+    uint32_t V;
+    uint64_t* edge;  // V
+};
+
+__global__ void __launch_bounds__(kWeldBlock) k_weld_edges(WeldEdgeParams q) {
+    __shared__ uint32_t sStart[kShards + 1];
+    if (threadIdx.x == 0) {
+        uint32_t at = 0;
+        for (int k = 0; k < kShards; ++k) {
+            sStart[k] = at;
+            at += q.shardV[k];
+        }
+        sStart[kShards] = at;
+    }
+    __syncthreads();
+    const uint32_t r = blockIdx.x * kWeldBlock + threadIdx.x;
+    if (r >= sStart[kShards]) return;
+    uint32_t shard = 0;
+    for (uint32_t step = kShards / 2; step; step >>= 1)
+        if (sStart[shard + step] <= r) shard += step;
+    const VertexKey K = q.vk[(size_t)shard * q.vShardCap + (r - sStart[shard])];
+    if (K.w >= q.mpuCount) return;
+    const uint32_t gi = (uint32_t)q.offs[K.w] + (K.vidKey & 0xffffu);
+    if (gi >= q.V) return;
+    const uint32_t key = K.vidKey >> 16;
+    const uint32_t sx = key & 7u, sy = (key >> 3) & 7u, sz = (key >> 6) & 7u, ax = (key >> 9) & 3u;
+    const bool fx = sx == 0u || sx == 7u, fy = sy == 0u || sy == 7u, fz = sz == 0u || sz == 7u;
+    if (!((ax != 0u && fx) || (ax != 1u && fy) || (ax != 2u && fz))) return;  // interior: stays kEmptyKey
+    const uint32_t m = K.w + q.mpuBegin;
+    const uint32_t nyz = q.dims[1] * q.dims[2];
+    const uint32_t i = m / nyz, jk = m - i * nyz;
+    const uint32_t j = jk / q.dims[2], k = jk - j * q.dims[2];
+    q.edge[gi] = ((((uint64_t)(7u * i + sx) << kCoordBits | (uint64_t)(7u * j + sy)) << kCoordBits |
+                   (uint64_t)(7u * k + sz)) << 2) | ax;
+}
+
+// k_weld_mark over the gathered vertices' edge ids: one lane per vertex, the same insert
+__global__ void __launch_bounds__(kWeldBlock) k_weld_mark_ids(WeldParams q, const uint64_t* __restrict__ edge) {
+    const uint32_t gi = blockIdx.x * kWeldBlock + threadIdx.x;
+    if (gi >= q.V) return;
+    const uint64_t id = edge[gi];
+    if (id == kEmptyKey) {
+        q.rep[gi] = kNoSlot;
+        return;
+    }
+    uint32_t slot = weld_hash(id) & q.tableMask;
     for (uint32_t tries = 0; tries <= q.tableMask; ++tries) {
         const uint64_t seen = atomicCAS((unsigned long long*)&q.keys[slot], (unsigned long long)kEmptyKey,
                                         (unsigned long long)id);
@@ -287,21 +366,126 @@ hipError_t weld_grow(T*& ptr, size_t& cap, size_t need) {
 const char* kWeldPhaseNames[kWeldPhases] = {"weld total", "table fill + k_weld_mark", "k_weld_resolve", "k_weld_scan",
                                             "k_weld_emit", "k_weld_map"};
 
+// the run's vertex records per shard (its host counters): one record per vertex, every shard
+// within its capacity (finish re-runs until they fit)
+int weld_shard_counts(const psgpu_ctx* c, uint32_t V, uint32_t* shardV) {
+    uint64_t recs = 0;
+    for (int k = 0; k < kShards; ++k) {
+        shardV[k] = c->hostCtr->shard[k].v;
+        if (shardV[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;
+        recs += shardV[k];
+    }
+    return recs == V ? PSGPU_RET_SUCCESS : PSGPU_RET_DEVICE_ERROR;
+}
+
+// Sizes the table for V > 0 input vertices, grows W's buffers to V vertices and T triangles and
+// points q at them (the table, rep / kid / blockCnt / map, the welded arrays, the grid sizes).
+int weld_prepare(WeldState& W, uint32_t V, uint32_t T, WeldParams& q, uint32_t* slotsOut) {
+    // at most V seam records: a table of >= 2 V slots stays at most half full
+    uint32_t slots = 1024;
+    while (slots < 2ull * V && slots < (1u << 31)) slots <<= 1;
+    const uint32_t blocks = (V + kWeldBlock - 1) / kWeldBlock;
+    size_t capV3n = W.capV3, capV3c = W.capV3, capVk = W.capV, capVm = W.capV;
+    PSGPU_CHECK(weld_grow(W.table, W.capTable, (size_t)slots * 12));
+    PSGPU_CHECK(weld_grow(W.rep, W.capV, (size_t)V + 4));
+    PSGPU_CHECK(weld_grow(W.kid, capVk, (size_t)V + 4));
+    PSGPU_CHECK(weld_grow(W.map, capVm, (size_t)V + 4));
+    PSGPU_CHECK(weld_grow(W.blockCnt, W.capBlocks, (size_t)blocks + 1));
+    PSGPU_CHECK(weld_grow(W.pos, W.capV3, (size_t)V * 3));
+    PSGPU_CHECK(weld_grow(W.nrm, capV3n, (size_t)V * 3));
+    PSGPU_CHECK(weld_grow(W.col, capV3c, (size_t)V * 3));
+    PSGPU_CHECK(weld_grow(W.tris, W.capT3, (size_t)T * 3 + 4));
+    q.V = V;
+    q.T = T;
+    q.keys = reinterpret_cast<uint64_t*>(W.table);
+    q.mins = reinterpret_cast<uint32_t*>(W.table + (size_t)slots * 8);
+    q.tableMask = slots - 1u;
+    q.rep = W.rep;
+    q.kid = W.kid;
+    q.blockCnt = W.blockCnt;
+    q.blocks = blocks;
+    q.wpos = W.pos;
+    q.wnrm = W.nrm;
+    q.wcol = W.col;
+    q.wtris = W.tris;
+    q.map = W.map;
+    q.mapBlocks = (V + 4u * kWeldBlock - 1u) / (4u * kWeldBlock);
+    *slotsOut = slots;
+    return PSGPU_RET_SUCCESS;
+}
+
+// The launches after the mark, shared by psgpu_weld and a group's weld; ev (null: untimed): four
+// events, one recorded after each launch.
+int weld_after_mark(const WeldParams& q, hipStream_t s, hipEvent_t* ev) {
+    const uint32_t triBlocks = (uint32_t)(((uint64_t)q.T + 4ull * kWeldBlock - 1ull) / (4ull * kWeldBlock));
+    hipLaunchKernelGGL(k_weld_resolve, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
+    if (ev) PSGPU_CHECK(hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kWeldBlock), 0, s, q);
+    if (ev) PSGPU_CHECK(hipEventRecord(ev[1], s));
+    hipLaunchKernelGGL(k_weld_emit, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
+    if (ev) PSGPU_CHECK(hipEventRecord(ev[2], s));
+    hipLaunchKernelGGL(k_weld_map, dim3(q.mapBlocks + triBlocks), dim3(kWeldBlock), 0, s, q);
+    if (ev) PSGPU_CHECK(hipEventRecord(ev[3], s));
+    PSGPU_CHECK(hipGetLastError());
+    return PSGPU_RET_SUCCESS;
+}
+
+}  // namespace
+
 // the current run is finished, uncollected by nothing newer, and whole
 bool weld_run_ready(const psgpu_ctx* c) {
     return c && !c->pending && c->haveResult && c->finishedSeq == c->runSeq;
 }
 
-}  // namespace
-
-void weld_free(psgpu_ctx* c) {
-    WeldState& W = c->weld;
+void weld_state_free(WeldState& W) {
     void* bufs[] = {W.table, W.rep, W.kid, W.map, W.blockCnt, W.pos, W.nrm, W.col, W.tris};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : W.ev)
         if (e) (void)hipEventDestroy(e);
     W = WeldState{};
+}
+
+void weld_free(psgpu_ctx* c) { weld_state_free(c->weld); }
+
+int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s) {
+    const uint32_t V = c->info.ctVertices;
+    if (V == 0) return PSGPU_RET_SUCCESS;
+    WeldEdgeParams q;
+    memset(&q, 0, sizeof(q));
+    const int rc = weld_shard_counts(c, V, q.shardV);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    q.vk = c->vk;
+    q.offs = c->offs;
+    q.vShardCap = c->vShardCap;
+    for (int a = 0; a < 3; ++a) q.dims[a] = c->dims[a];
+    q.mpuBegin = c->mpuBegin;
+    q.mpuCount = c->mpuCount;
+    q.V = V;
+    q.edge = edge;
+    PSGPU_CHECK(hipMemsetAsync(edge, 0xff, (size_t)V * 8, s));
+    hipLaunchKernelGGL(k_weld_edges, dim3((V + kWeldBlock - 1) / kWeldBlock), dim3(kWeldBlock), 0, s, q);
+    PSGPU_CHECK(hipGetLastError());
+    return PSGPU_RET_SUCCESS;
+}
+
+int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals) {
+    WeldParams q;
+    memset(&q, 0, sizeof(q));
+    uint32_t slots = 0;
+    const int rc = weld_prepare(W, in.V, in.T, q, &slots);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    q.pos = in.pos;
+    q.nrm = in.nrm;
+    q.col = in.col;
+    q.tris = in.tris;
+    PSGPU_CHECK(hipMemsetAsync(W.table, 0xff, (size_t)slots * 12, s));
+    hipLaunchKernelGGL(k_weld_mark_ids, dim3(q.blocks), dim3(kWeldBlock), 0, s, q, in.edge);
+    if (ev) PSGPU_CHECK(hipEventRecord(ev[0], s));
+    const int rt = weld_after_mark(q, s, ev ? ev + 1 : nullptr);
+    if (rt != PSGPU_RET_SUCCESS) return rt;
+    PSGPU_CHECK(hipMemcpyAsync(totals, W.blockCnt + q.blocks, sizeof(*totals), hipMemcpyDeviceToHost, s));
+    return PSGPU_RET_SUCCESS;
 }
 
 }  // namespace psgpu
@@ -331,75 +515,35 @@ int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
     }
     WeldParams q;
     memset(&q, 0, sizeof(q));
-    uint64_t recs = 0;
-    for (int k = 0; k < kShards; ++k) {
-        q.shardV[k] = c->hostCtr->shard[k].v;
-        if (q.shardV[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;  // finish re-runs until they fit
-        recs += q.shardV[k];
-    }
-    if (recs != V) return PSGPU_RET_DEVICE_ERROR;  // one record per vertex
-    // at most V seam records: a table of >= 2 V slots stays at most half full
-    uint32_t slots = 1024;
-    while (slots < 2ull * V && slots < (1u << 31)) slots <<= 1;
-    const uint32_t blocks = (V + kWeldBlock - 1) / kWeldBlock;
-    size_t capV3n = W.capV3, capV3c = W.capV3, capVk = W.capV, capVm = W.capV;
-    PSGPU_CHECK(weld_grow(W.table, W.capTable, (size_t)slots * 12));
-    PSGPU_CHECK(weld_grow(W.rep, W.capV, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.kid, capVk, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.map, capVm, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.blockCnt, W.capBlocks, (size_t)blocks + 1));
-    PSGPU_CHECK(weld_grow(W.pos, W.capV3, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.nrm, capV3n, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.col, capV3c, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.tris, W.capT3, (size_t)T * 3 + 4));
+    rc = weld_shard_counts(c, V, q.shardV);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    uint32_t slots = 0;
+    rc = weld_prepare(W, V, T, q, &slots);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
     q.vk = c->vk;
     q.offs = c->offs;
     q.vShardCap = c->vShardCap;
     for (int a = 0; a < 3; ++a) q.dims[a] = c->dims[a];
     q.mpuBegin = c->mpuBegin;
     q.mpuCount = c->mpuCount;
-    q.V = V;
-    q.T = T;
-    q.keys = reinterpret_cast<uint64_t*>(W.table);
-    q.mins = reinterpret_cast<uint32_t*>(W.table + (size_t)slots * 8);
-    q.tableMask = slots - 1u;
-    q.rep = W.rep;
-    q.kid = W.kid;
-    q.blockCnt = W.blockCnt;
-    q.blocks = blocks;
     q.pos = c->pos;
     q.nrm = c->nrm;
     q.col = c->col;
     q.tris = c->tris;
-    q.wpos = W.pos;
-    q.wnrm = W.nrm;
-    q.wcol = W.col;
-    q.wtris = W.tris;
-    q.map = W.map;
-    q.mapBlocks = (V + 4u * kWeldBlock - 1u) / (4u * kWeldBlock);
-    const uint32_t triBlocks = (uint32_t)(((uint64_t)T + 4ull * kWeldBlock - 1ull) / (4ull * kWeldBlock));
     hipStream_t s = c->stream;
     const bool timed = c->timing != 0;
     if (timed)
         for (hipEvent_t& e : W.ev)
             if (!e) PSGPU_CHECK(hipEventCreate(&e));
-    int ev = 0;
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
+    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[0], s));
     // every key empty (all ones), every minimum 0xffffffff
     PSGPU_CHECK(hipMemsetAsync(W.table, 0xff, (size_t)slots * 12, s));
-    hipLaunchKernelGGL(k_weld_mark, dim3(blocks), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
-    hipLaunchKernelGGL(k_weld_resolve, dim3(blocks), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
-    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
-    hipLaunchKernelGGL(k_weld_emit, dim3(blocks), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
-    hipLaunchKernelGGL(k_weld_map, dim3(q.mapBlocks + triBlocks), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[ev++], s));
-    PSGPU_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_weld_mark, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
+    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[1], s));
+    rc = weld_after_mark(q, s, timed ? W.ev + 2 : nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
     uint64_t totals = 0;
-    PSGPU_CHECK(hipMemcpyAsync(&totals, W.blockCnt + blocks, sizeof(totals), hipMemcpyDeviceToHost, s));
+    PSGPU_CHECK(hipMemcpyAsync(&totals, W.blockCnt + q.blocks, sizeof(totals), hipMemcpyDeviceToHost, s));
     PSGPU_CHECK(hipStreamSynchronize(s));
     if (timed) {
         (void)hipEventElapsedTime(&W.lastMs[0], W.ev[0], W.ev[kWeldPhases - 1]);

@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
     "psgpu_vertex_queue", "psgpu_mpu_masks",
+    "psgpu_group_weld", "psgpu_group_weld_device", "psgpu_group_download_weld", "psgpu_group_weld_times",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -187,6 +188,10 @@ def load(build_if_missing: bool = True):
         "psgpu_weld_device": ([vp, ctypes.POINTER(PsWeldDevice)], i32),
         "psgpu_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
         "psgpu_weld_times": ([vp, vp, i32, vp], i32),
+        "psgpu_group_weld": ([vp, i32, ctypes.POINTER(PsWeldInfo)], i32),
+        "psgpu_group_weld_device": ([vp, ctypes.POINTER(PsWeldDevice)], i32),
+        "psgpu_group_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
+        "psgpu_group_weld_times": ([vp, vp, i32, vp], i32),
         "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
         "psgpu_mpu_masks": ([vp, vp, vp, u32], i32),
     }
@@ -686,6 +691,42 @@ class Group:
         d = PsMeshDevice()
         _check(self._L.psgpu_group_gather(self._g, dst_part, ctypes.byref(d)), "psgpu_group_gather")
         return d
+
+    def weld_info(self, dst_part: int = 0) -> PsWeldInfo:
+        """psgpu_group_weld on the group's run (a pending one is finished first): the parts
+        welded into one watertight mesh in HBM of part `dst_part`'s device (``weld_device()``);
+        returns its counts."""
+        info = PsWeldInfo()
+        _check(self._L.psgpu_group_weld(self._g, dst_part, ctypes.byref(info)), "psgpu_group_weld")
+        return info
+
+    def weld(self, dst_part: int = 0) -> WeldedMesh:
+        """Weld the group's run on the device and download the watertight indexed mesh: the
+        same bytes as ``Polygonizer.weld()`` of the whole lattice on one context."""
+        info = self.weld_info(dst_part)
+        V, T, Vin = info.ctVertices, info.ctTriangles, info.ctInputVertices
+        pos = np.zeros((V, 3), np.float32)
+        nrm = np.zeros((V, 3), np.float32)
+        col = np.zeros((V, 3), np.float32)
+        tris = np.zeros((T, 3), np.uint32)
+        vmap = np.zeros(Vin, np.uint32)
+        _check(self._L.psgpu_group_download_weld(self._g, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data,
+                                                 tris.ctypes.data, vmap.ctypes.data), "psgpu_group_download_weld")
+        return WeldedMesh(pos, nrm, col, tris, vmap, info)
+
+    def weld_device(self) -> PsWeldDevice:
+        """Device pointers of the last weld of the current run (valid until the next weld)."""
+        d = PsWeldDevice()
+        _check(self._L.psgpu_group_weld_device(self._g, ctypes.byref(d)), "psgpu_group_weld_device")
+        return d
+
+    def weld_times(self) -> dict:
+        """hipEvent times (ms) of the last weld (OPT_KERNEL_TIMING on the group): the whole weld,
+        the gather, the parts' edge ids and their copies, the mark and the four launches after it."""
+        ms = (ctypes.c_float * 8)()
+        names = (ctypes.c_char_p * 8)()
+        n = self._L.psgpu_group_weld_times(self._g, ms, 8, names)
+        return {names[i].decode(): ms[i] for i in range(n)}
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info, _ = self.finish()

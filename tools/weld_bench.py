@@ -11,20 +11,107 @@ It also prints the welded counts and the open edges each weld leaves.  Output co
 profiles/weld_c3.txt (DESIGN.md §6 "Weld").
 
     python3 tools/weld_bench.py [CONFIG]
+
+With --parts N the same input runs as a Group of N parts on device 0 (the default, planned
+split) and psgpu_group_weld is timed the same way, each of its phases, beside the
+single-context weld of the same input in the same process and the only route a group had
+before: Group.download() + meshio.weld.  Output of --parts 1, 2 and 8 committed as
+profiles/group_weld_c3.txt (DESIGN.md §6 "Weld of a group").
+
+    python3 tools/weld_bench.py [CONFIG] --parts N
 """
+import argparse
 import os
 import statistics
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
 from parsip_amd import gpu, meshio, synth  # noqa: E402
 
 WARMUP, REPS, HOST_REPS = 5, 20, 3
 
 
+def timed_welds(weld_info, weld_times):
+    """Per-phase hipEvent times and the blocking call's wall time (ms) of REPS welds after WARMUP."""
+    rows, wall, winfo = [], [], None
+    for k in range(WARMUP + REPS):
+        t0 = time.perf_counter()
+        winfo = weld_info()
+        t1 = time.perf_counter()
+        if k >= WARMUP:
+            rows.append(weld_times())
+            wall.append((t1 - t0) * 1e3)
+    return rows, wall, winfo
+
+
+def print_phases(rows):
+    for phase in rows[0]:
+        vals = [r[phase] for r in rows]
+        print(f"  {phase:28s} {statistics.median(vals):8.4f}   (min {min(vals):.4f}, max {max(vals):.4f})")
+
+
+def group_main(name, parts):
+    model, cs, _ = synth.make_config(name)
+    poly = gpu.Polygonizer(0)
+    poly.set_option(gpu.OPT_KERNEL_TIMING, 1)
+    poly.set_model(model)
+    info = poly.run(cs)
+    print(f"{name}: cellsize {cs}, {info.ctMPUs} MPUs, {info.ctVertices} vertices, {info.ctTriangles} triangles")
+    rows, wall, _ = timed_welds(poly.weld_info, poly.weld_times)
+    print(f"single-context weld, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms):")
+    print_phases(rows)
+    print(f"  {'psgpu_weld call, wall':28s} {statistics.median(wall):8.4f}")
+    one_ms = statistics.median([r["weld total"] for r in rows])
+    one = poly.weld()
+
+    g = gpu.Group([0] * parts)
+    g.set_option(gpu.OPT_KERNEL_TIMING, 1)
+    g.set_model(model)
+    total, pinfo = g.run(cs)
+    print(f"group of {parts} part(s) on device 0, MPU bounds {g.split().tolist()}, "
+          f"vertices per part {[p.info.ctVertices for p in pinfo]}")
+    rows, wall, winfo = timed_welds(g.weld_info, g.weld_times)
+    print(f"group weld, median of {REPS} after {WARMUP} warm-ups (hipEvents on the gathering stream, ms):")
+    print_phases(rows)
+    print(f"  {'psgpu_group_weld call, wall':28s} {statistics.median(wall):8.4f}   (launches + wait + the counts' read-back)")
+    med = {ph: statistics.median([r[ph] for r in rows]) for ph in rows[0]}
+    grp_ms = med["group weld total"]
+    top = max((ph for ph in med if ph != "group weld total"), key=lambda ph: med[ph])
+    print(f"  largest phase: {top} ({med[top]:.4f} ms, {100 * med[top] / grp_ms:.0f} % of the total)")
+    w = g.weld()
+    same = all(np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+               for a, b in ((w.pos, one.pos), (w.nrm, one.nrm), (w.col, one.col), (w.tris, one.tris),
+                            (w.vertex_map, one.vertex_map)))
+    print(f"group weld: {winfo.ctInputVertices} -> {winfo.ctVertices} vertices ({winfo.ctSeamVertices} on MPU faces), "
+          f"{winfo.ctTriangles} triangles, {meshio.open_edge_count(w.tris)} open edges; "
+          f"bytes equal the single-context weld: {bool(same)}")
+
+    ts, wb = [], None
+    for _ in range(HOST_REPS):
+        t0 = time.perf_counter()
+        wb = meshio.weld(meshio.from_mesh(g.download()))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    host_ms = statistics.median(ts)
+    print(f"host route, median of {HOST_REPS} (wall, ms):")
+    print(f"  {'Group.download() + meshio.weld':36s} {host_ms:10.2f}   -> {wb.n_vertices} vertices, "
+          f"{meshio.open_edge_count(wb.tris)} open edges")
+    print(f"group weld / single-context weld: {grp_ms / one_ms:.2f}x; "
+          f"Group.download() + meshio.weld / group weld: {host_ms / grp_ms:.0f}x")
+    g.close()
+    poly.close()
+
+
 def main():
-    name = sys.argv[1] if len(sys.argv) > 1 else "C3"
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("config", nargs="?", default="C3")
+    ap.add_argument("--parts", type=int, default=0, help="run as a Group of N parts on device 0 and time psgpu_group_weld")
+    args = ap.parse_args()
+    if args.parts > 0:
+        return group_main(args.config, args.parts)
+    name = args.config
     model, cs, _ = synth.make_config(name)
     lo, hi = model.bbox
     poly = gpu.Polygonizer(0)
@@ -34,18 +121,9 @@ def main():
     print(f"{name}: cellsize {cs}, {info.ctMPUs} MPUs, {info.ctVertices} vertices, {info.ctTriangles} triangles")
     print("polygonization kernels (ms): " + ", ".join(f"{k} {v:.4f}" for k, v in poly.kernel_times().items()))
 
-    rows, wall = [], []
-    for k in range(WARMUP + REPS):
-        t0 = time.perf_counter()
-        winfo = poly.weld_info()
-        t1 = time.perf_counter()
-        if k >= WARMUP:
-            rows.append(poly.weld_times())
-            wall.append((t1 - t0) * 1e3)
+    rows, wall, winfo = timed_welds(poly.weld_info, poly.weld_times)
     print(f"device weld, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms):")
-    for phase in rows[0]:
-        vals = [r[phase] for r in rows]
-        print(f"  {phase:28s} {statistics.median(vals):8.4f}   (min {min(vals):.4f}, max {max(vals):.4f})")
+    print_phases(rows)
     print(f"  {'psgpu_weld call, wall':28s} {statistics.median(wall):8.4f}   (launches + wait + the counts' read-back)")
     dev_ms = statistics.median([r["weld total"] for r in rows])
 
