@@ -182,6 +182,7 @@ typedef struct PsMeshInfo {
 #define PSGPU_LAUNCH_SURFACE    2u  /* k_vertex + k_finish ran as one launch (k_surface)         */
 #define PSGPU_LAUNCH_FRONT      4u  /* k_precheck + k_mpu ran as one launch (k_front)            */
 #define PSGPU_LAUNCH_RERUN      8u  /* finish re-ran the run (grid / capacity / protocol error)  */
+#define PSGPU_LAUNCH_SIEVE     16u  /* k_sieve ran ahead of S1 (no S1 wave for a dead brick)      */
 
 /* Device-resident compact mesh of the last polygonization (pointers into the
  * context's HBM buffers; valid until the next psgpu_polygonize on the context).
@@ -322,6 +323,10 @@ int  psgpu_vertex_queue(psgpu_ctx* ctx, uint32_t* counts, uint32_t* recs, uint32
  * bit k: op k; PSGPU_OPT_OP_INSIDE), zeros for an MPU that was not queued or a run without
  * culling.  capacity is in MPUs; PSGPU_RET_PARAM_ERROR if it is short. */
 int  psgpu_mpu_masks(psgpu_ctx* ctx, uint8_t* queued, uint64_t* masks, uint32_t capacity);
+/* Debug export of the finished run's live bricks (k_sieve's list, in list order): count receives
+ * their number (0 when the run took no sieve: PSGPU_LAUNCH_SIEVE), bricks (may be null) 3 words
+ * per brick, its lattice brick coordinates (x, y, z: MPU coordinates / 2). */
+int  psgpu_live_bricks(psgpu_ctx* ctx, uint32_t* bricks, uint32_t capacity, uint32_t* count);
 /* PrintThreadResults (PS_Polygonizer.h:393, body .cpp:414-428, counters .cpp:443-469).
  * The reference keeps one (processed, crossed) MPU count pair per TBB worker that ran an
  * MPU, accumulated over every Polygonize of the process.  Here the worker is a device
@@ -440,6 +445,14 @@ int  psgpu_set_option(psgpu_ctx* ctx, int option, int64_t value);
                                        CU (C3 and its shares, not C5's 512^3 frame); env
                                        PSGPU_FRONT; never with PSGPU_OPT_MPU_TICKS, nor while
                                        more than 3 other contexts have runs pending on the device */
+#define PSGPU_OPT_SIEVE        24   /* k_sieve ahead of S1: a 2x2x2 brick of MPUs over whose corner box
+                                       every primitive the root needs is culled gets its S1 result
+                                       (nothing passes) from one lane of the sieve and no S1 wave:
+                                       0 (default) never, 1 whenever culling is on and the model
+                                       allows it, 2 as 1 unless the run is alone on the device; env
+                                       PSGPU_SIEVE; never with PSGPU_OPT_MPU_TICKS.  Identical output.
+                                       Off by default: the extra launch cost C3's step more than the
+                                       dead bricks' S1 waves did */
 #define PSGPU_OPT_MPU_TICKS    19   /* 1: runs record per-MPU ticks for MPUSTATS
                                        (psgpu_download_process_stats); 0 (default) off */
 #define PSGPU_OPT_JIT_ASYNC    11   /* 1 (default): set_model returns at once; hiprtc compiles the
@@ -450,6 +463,11 @@ int  psgpu_set_option(psgpu_ctx* ctx, int option, int64_t value);
  * code-object size or a negative error (log receives the compiler output). */
 long psgpu_jit_compile(const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* matrices,
                        const PsSoaBlobOps* ops, int mode, char* log, size_t cap);
+/* Host-only (no GPU): the device image of a model (psgpu::DevModel: the walk program, the
+ * culling segments, the root-zero set) into out when cap holds it; returns its size in bytes
+ * or a negative error.  For tests that compile psgpu_model.h as plain C++. */
+long psgpu_model_image(const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* matrices,
+                       const PsSoaBlobOps* ops, void* out, size_t cap);
 /* 1 if the current model runs on run-time specialised kernels, 0 on the interpreter. */
 int  psgpu_jit_active(psgpu_ctx* ctx);
 /* 1 while the current model's specialised kernels are still compiling. */

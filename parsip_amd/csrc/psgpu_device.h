@@ -393,27 +393,14 @@ __device__ __forceinline__ CullLanes load_cull_lanes(ModelPtr M) {
     return L;
 }
 
-// Is the segment's primitive exactly +0 over the box (centre c, half-diagonal h)?
-__device__ __forceinline__ bool cull_one(const CullSeg& S, float cx, float cy, float cz, float h) {
-    const float dx = cx - S.a[0], dy = cy - S.a[1], dz = cz - S.a[2];
-    const float t = (dx * S.u[0] + dy * S.u[1] + dz * S.u[2]) * S.invUU;
-    const float lx = dx - t * S.u[0], ly = dy - t * S.u[1], lz = dz - t * S.u[2];
-    const float lineDist = __builtin_amdgcn_sqrtf(lx * lx + ly * ly + lz * lz);
-    const float tc = fminf(fmaxf(t, S.tmin), S.tmax);
-    const float ex = dx - tc * S.u[0], ey = dy - tc * S.u[1], ez = dz - tc * S.u[2];
-    const float d = (__builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) - S.radius) - h;
-    return d > 0.0f && d * d >= 1.02f && (lineDist - h > S.axisClear);
-}
-
+// cull_one / cull_box: psgpu_model.h (host and device)
 __device__ __forceinline__ CullMask cull_mask_from(const CullLanes& L, float x0, float y0, float z0, float x1,
                                                    float y1, float z1) {
     CullMask cm{0ull, 0ull};
-    if (!(x1 - x0 < 1e30f && y1 - y0 < 1e30f && z1 - z0 < 1e30f)) return cm;
-    const float cx = 0.5f * (x0 + x1), cy = 0.5f * (y0 + y1), cz = 0.5f * (z0 + z1);
-    const float hx = 0.5f * (x1 - x0), hy = 0.5f * (y1 - y0), hz = 0.5f * (z1 - z0);
-    const float h = __builtin_amdgcn_sqrtf(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-6f;
-    cm.lo = ballot(cull_one(L.s[0], cx, cy, cz, h));
-    if (L.two) cm.hi = ballot(cull_one(L.s[1], cx, cy, cz, h));
+    float c[3], h;
+    if (!cull_box(x0, y0, z0, x1, y1, z1, c, &h)) return cm;
+    cm.lo = ballot(cull_one(L.s[0], c[0], c[1], c[2], h));
+    if (L.two) cm.hi = ballot(cull_one(L.s[1], c[0], c[1], c[2], h));
     return cm;
 }
 
@@ -805,7 +792,7 @@ __device__ __forceinline__ uint32_t front_tag(const Params& p) { return p.ctr->e
 
 template <class EV, int SPLIT = 1, bool FRONT = false>
 __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
-    const int wave = wave_index();
+    const int wave = (int)uniform((uint32_t)wave_index());  // scalar: so are its brick slot and tree part
     const int lane = lane_id();
     const int part = wave % SPLIT;  // subtree of the root this wave walks (SPLIT 2)
     const int slot = wave / SPLIT;  // the block's brick
@@ -821,15 +808,38 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     CullLanes cl;  // loaded first: independent of everything below
     if (p.cull) cl = load_cull_lanes(as_const(p.model));
     const uint32_t W = blockIdx.x * (4u / SPLIT) + (uint32_t)slot;  // brick slot: decides the queue shard
+    uint32_t Wq = W;  // ... from this copy, which the split kernels keep in a vector register across
+    if constexpr (SPLIT == 2) asm volatile("" : "+v"(Wq));  // the walk: they have no scalar one to spare
     const uint32_t bzN = p.brickDims[2], byN = p.brickDims[1];
     const uint32_t nBricks = p.brickDims[0] * byN * bzN;
-    const uint32_t B = W < nBricks ? (uint32_t)(((uint64_t)W * p.brickStride) % nBricks) : W;  // its brick
+    // The wave's brick (lattice brick coordinates).  After k_sieve: entry W of its list of live
+    // bricks; a wave past the list has nothing to do (a dead brick's MPUs were written by the
+    // sieve).  Otherwise brick W, or with the spreading permutation (W * brickStride) mod bricks.
+    uint32_t bi, bj, bk;
+    bool idle = W >= nBricks;
+    if (p.sieve) {
+        // written by the launch before this one: read as constants (uniform: two scalar loads, issued together)
+        typedef const __attribute__((address_space(4))) uint64_t* CU64;
+        typedef const __attribute__((address_space(4))) uint32_t* CU32;
+        const uint64_t e = W < nBricks ? ((CU64)p.liveList)[W] : 0ull;
+        idle = W >= *(CU32)&p.ctr->liveBricks;
+        bi = (uint32_t)e & 0x1fffffu;
+        bj = (uint32_t)(e >> 21) & 0x1fffffu;
+        bk = (uint32_t)(e >> 42);
+    } else {
+        const uint32_t B =
+            (idle || p.brickStride == 1u) ? W : (uint32_t)(((uint64_t)W * p.brickStride) % nBricks);
+        uint32_t jk;
+        bi = p.brickI0 + div_by(B, byN * bzN, p.brickMagic[1], &jk);
+        bj = div_by(jk, bzN, p.brickMagic[0], &bk);
+    }
+    if (SPLIT == 1 && idle) return;  // (the split's waves stay for their block's barriers)
     const uint32_t g = (uint32_t)lane >> 3;
-    const uint32_t mi = 2u * (p.brickI0 + B / (byN * bzN)) + ((g >> 2) & 1u);
-    const uint32_t mj = 2u * ((B / bzN) % byN) + ((g >> 1) & 1u);
-    const uint32_t mk = 2u * (B % bzN) + (g & 1u);
+    const uint32_t mi = 2u * bi + ((g >> 2) & 1u);
+    const uint32_t mj = 2u * bj + ((g >> 1) & 1u);
+    const uint32_t mk = 2u * bk + (g & 1u);
     const uint32_t mg = (mi * p.dims[1] + mj) * p.dims[2] + mk;
-    const bool valid = W < nBricks && mi < p.dims[0] && mj < p.dims[1] && mk < p.dims[2] && mg >= p.mpuBegin &&
+    const bool valid = !idle && mi < p.dims[0] && mj < p.dims[1] && mk < p.dims[2] && mg >= p.mpuBegin &&
                        mg - p.mpuBegin < p.mpuCount;
     // A lane without an MPU of the range (a brick over the lattice's high faces or a range
     // end) takes the origin of the nearest lattice MPU, so the wave's culling box stays the
@@ -837,20 +847,23 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     // the domain, every primitive stays live and those waves walk 3-5x longer (r03 timeline).
     const uint32_t ci = min(mi, p.dims[0] - 1u), cj = min(mj, p.dims[1] - 1u), ck = min(mk, p.dims[2] - 1u);
     const uint32_t m = valid ? mg : (ci * p.dims[1] + cj) * p.dims[2] + ck;
-    float o[3];
-    mpu_origin(p, m, o);
+    const float o[3] = {p.lo[0] + (float)ci * p.side, p.lo[1] + (float)cj * p.side,
+                        p.lo[2] + (float)ck * p.side};  // mpu_origin(m), its coordinates at hand
     const int c = lane & 7;
     const float X = (float)(c & 1), Y = (float)((c >> 1) & 1), Z = (float)(c >> 2);
     const float px = X * p.side + o[0];
     const float py = Y * p.side + o[1];
     const float pz = Z * p.side + o[2];
+    // the wave's culling box: its 64 corners' (brick_box, wave-uniform: no wave reductions)
+    float blo[3], bhi[3];
+    brick_box(p.lo, p.side, p.dims, bi, bj, bk, blo, bhi);
     float f = -1.0f;
     CullMask cm{0ull, 0ull};
+    if (p.cull) cm = cull_mask_from(cl, blo[0], blo[1], blo[2], bhi[0], bhi[1], bhi[2]);
     if constexpr (SPLIT == 2) {
         __shared__ float sF[4][64];
-        cm = cull_mask_points(cl, px, py, pz, p.cull != 0);
         float fp = -1.0f;
-        if (!(p.debug & 8u)) {
+        if (!(p.debug & 8u) && !idle) {
             if (part == 0) ev.template evaln_part<4, false, 1, 0>(&px, &py, &pz, cm, &fp, nullptr);
             else ev.template evaln_part<4, false, 1, 1>(&px, &py, &pz, cm, &fp, nullptr);
         }
@@ -859,10 +872,8 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
         const float rv = sF[slot * 2][lane], lv = sF[slot * 2 + 1][lane];
         if (!(p.debug & 8u)) ev.template combine<false, 1>(&rv, nullptr, &lv, nullptr, cm, &f, nullptr);
     } else if (!(p.debug & 8u)) {  // ablation bit 3: S1 without the walk (nothing passes)
-        cm = cull_mask_points(cl, px, py, pz, p.cull != 0);
         f = ev.template eval<4, false>(px, py, pz, cm, nullptr);
     } else if (p.debug & 16u) {  // bit 4: the culling mask only
-        cm = cull_mask_points(cl, px, py, pz, p.cull != 0);
         f = (float)(cm.lo & 1ull) - 1.0f;
     }
     const uint64_t bal = ballot(valid && f > 0.0f);
@@ -960,7 +971,7 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
         if (p.mpuTicks) mpu_ticks_s1(p, mOf - p.mpuBegin, tick0);
     }
     if (flags8 == 0u) return;
-    const uint32_t shard = W / (p.pShardCap / 8u);
+    const uint32_t shard = Wq / (p.pShardCap / 8u);
     if (lane == 1 && proven8 != 0u) atomicAdd(&p.ctr->shard[shard].b, (uint32_t)__popc(proven8));
     if (queue8 == 0u) return;
     // k_front: the block's sub-queue (blockIdx mod 8, the XCD of round-robin placement: a speed

@@ -367,6 +367,9 @@ int build_device_model(const PsSoaBlobPrims& P, const PsSoaPrimMatrices& Mx, con
         }
     }
     D.boundable = bnd ? 1u : 0u;
+    // the primitives that, all culled over a box, leave the root exactly +0 there (k_sieve)
+    D.rootZeroValid = root_zero_set(D, D.rootZero) ? 1u : 0u;
+    if (!D.rootZeroValid) D.rootZero[0] = D.rootZero[1] = 0ull;
     return PSGPU_RET_SUCCESS;
 }
 
@@ -448,6 +451,7 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
     const size_t nq = std::max<size_t>((size_t)c->pShardCap * kShards, fq);
     PSGPU_CHECK(grow(c->pq, c->capList, nq));
     PSGPU_CHECK(grow(c->pqMask, c->capPqMask, nq * 4));  // culling + op-inside mask per entry
+    PSGPU_CHECK(grow(c->liveList, c->capLive, brick_count(c)));  // k_sieve: at most every brick
     if (fq > c->capFq) {  // ready words start at 0: no run's tag
         PSGPU_CHECK(grow(c->fqReady, c->capFq, fq));
         PSGPU_CHECK(hipMemset(c->fqReady, 0, c->capFq * sizeof(uint32_t)));
@@ -481,6 +485,11 @@ LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
     in.crowded = c->crowded;
     in.mpuTicks = c->mpuTicksOpt != 0;
     in.splittable = c->splittable;
+    // k_sieve: with culling on, a root-zero set, and brick coordinates that fit a list entry
+    uint32_t bi0, bd[3];
+    brick_layout(c, &bi0, bd);
+    in.sievable = c->cull != 0 && c->model.rootZeroValid != 0u && (uint64_t)bi0 + bd[0] <= (1u << 21) &&
+                  bd[1] <= (1u << 21) && bd[2] <= (1u << 21);
     if (const JitKernels* J = c->jit.get()) {
         in.jit = true;
         in.hasPrecheckS = J->precheckS != nullptr;
@@ -513,6 +522,10 @@ Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
     brick_layout(c, &p.brickI0, p.brickDims);
     p.preBlocks = plan.preBlocks;
     p.brickStride = brick_stride((uint32_t)brick_count(c), (c->debug & 16384) != 0);
+    p.brickMagic[0] = p.brickDims[2] ? 0xffffffffu / p.brickDims[2] : 0u;
+    p.brickMagic[1] = (p.brickDims[2] * p.brickDims[1]) ? 0xffffffffu / (p.brickDims[2] * p.brickDims[1]) : 0u;
+    p.sieve = plan.sieve;
+    p.liveList = c->liveList;
     p.pq = c->pq;
     p.pqMask = c->pqMask;
     p.pShardCap = c->pShardCap;
@@ -568,6 +581,7 @@ int launch_all(psgpu_ctx* c, const Params& pin, const LaunchPlan& plan, hipStrea
     // the split kernel's blocks hold 2 MPUs, the others 4 (mpu_lds_bytes(0): 4 MPUs' LDS)
     const size_t mpuLds = mpu_lds_bytes(0) / (plan.split ? 2 : 1);
     if (timed) PSGPU_CHECK(hipEventRecord(c->ev[0], s));
+    if (plan.sieve) PSGPU_CHECK(launch_sieve(p, s));  // ahead of S1; counted with k_precheck's time
     if (plan.front) {  // S1 blocks, then S2 blocks taking the survivors as they are published
         PSGPU_CHECK(launch_jit(plan.split ? J->frontS : J->front, plan.preBlocks + plan.mpuBlocks, 256, mpuLds, s, p));
         if (timed) {
@@ -1036,6 +1050,7 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
     if (const char* e = getenv("PSGPU_MPU_MARGIN")) c->opt.mpuMarginDiv = std::max(1, atoi(e));
     if (const char* e = getenv("PSGPU_FUSED_SURFACE")) c->opt.fusedSurface = std::min(3, std::max(0, atoi(e)));
     if (const char* e = getenv("PSGPU_FRONT")) c->opt.front = std::min(2, std::max(0, atoi(e)));
+    if (const char* e = getenv("PSGPU_SIEVE")) c->opt.sieve = std::min(2, std::max(0, atoi(e)));
     *out = c;
     return PSGPU_RET_SUCCESS;
 }
@@ -1057,7 +1072,7 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->jit.reset();
     c->jit1.reset();
     weld_free(c);
-    void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
+    void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->liveList, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
                     c->pos, c->nrm, c->col, c->tris, c->ctr, c->totals, c->stamps, c->spans, c->mpuTicks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -1117,6 +1132,7 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
     else if (option == PSGPU_OPT_SPLIT_MAX_QUEUED && value >= 0 && value <= 0xffffffffll) c->opt.splitMaxQueued = (uint32_t)value;
     else if (option == PSGPU_OPT_FUSED_SURFACE && value >= 0 && value <= 3) c->opt.fusedSurface = (int)value;
     else if (option == PSGPU_OPT_FRONT && value >= 0 && value <= 2) c->opt.front = (int)value;
+    else if (option == PSGPU_OPT_SIEVE && value >= 0 && value <= 2) c->opt.sieve = (int)value;
     else if (option == PSGPU_OPT_TIER_RUNS && value >= 1 && value <= (1 << 30)) c->tierRuns = (int)value;
     else if (option == PSGPU_OPT_JIT) {
         if (value < 0 || value > 3) return PSGPU_RET_PARAM_ERROR;
@@ -1345,7 +1361,8 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
         I.ctLaneEvals = 8ull * c->mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
         I.launchFlags = c->mpuCount == 0 ? 0u
                         : (c->run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
-                              (c->run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u);
+                              (c->run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u) |
+                              (c->run.sieve ? PSGPU_LAUNCH_SIEVE : 0u);
         c->haveResult = true;
         c->finishedSeq = c->runSeq;
         if (c->countThreads) thread_results_add(c->serial, I.ctMPUs, I.ctSurfaceMPUs);
@@ -1408,6 +1425,28 @@ int psgpu_mpu_masks(psgpu_ctx* c, uint8_t* queued, uint64_t* masks, uint32_t cap
         queued[w] = queued[w] == 2 ? 1 : 0;
         if (!queued[w] || !c->cull)
             for (int k = 0; k < 4; ++k) masks[4 * w + k] = 0ull;
+    }
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_live_bricks(psgpu_ctx* c, uint32_t* bricks, uint32_t capacity, uint32_t* count) {
+    if (!c || !count) return PSGPU_RET_PARAM_ERROR;
+    int rc = psgpu_finish(c, nullptr);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    *count = 0;
+    if (c->mpuCount == 0 || !c->run.sieve) return PSGPU_RET_SUCCESS;
+    const uint32_t n = c->hostCtr->liveBricks;
+    *count = n;
+    if (!bricks || n == 0) return PSGPU_RET_SUCCESS;
+    if (n > capacity || n > c->capLive) return PSGPU_RET_PARAM_ERROR;
+    rc = set_device(c);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    std::vector<uint64_t> raw(n);
+    PSGPU_CHECK(hipMemcpy(raw.data(), c->liveList, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < n; ++k) {
+        bricks[3 * k] = (uint32_t)raw[k] & 0x1fffffu;
+        bricks[3 * k + 1] = (uint32_t)(raw[k] >> 21) & 0x1fffffu;
+        bricks[3 * k + 2] = (uint32_t)(raw[k] >> 42);
     }
     return PSGPU_RET_SUCCESS;
 }
@@ -2029,6 +2068,17 @@ long psgpu_jit_compile(const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* mat
         log[k] = 0;
     }
     return n < 0 ? PSGPU_RET_DEVICE_ERROR : n;
+}
+
+// Host-only: the device image of a model (DevModel, psgpu_model.h) as the kernels read it.
+long psgpu_model_image(const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* mats, const PsSoaBlobOps* ops,
+                       void* out, size_t cap) {
+    if (!prims || !mats || !ops) return PSGPU_RET_PARAM_ERROR;
+    std::unique_ptr<DevModel> m(new DevModel);
+    const int rc = build_device_model(*prims, *mats, *ops, *m);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    if (out && cap >= sizeof(DevModel)) memcpy(out, m.get(), sizeof(DevModel));
+    return (long)sizeof(DevModel);
 }
 
 // Whether the current model runs on run-time specialised kernels (1) or the interpreter (0).

@@ -110,6 +110,8 @@ struct psgpu_ctx {
     uint32_t* pq = nullptr;         // sharded S1 survivor queues
     uint64_t* pqMask = nullptr;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
     size_t capPqMask = 0;
+    uint64_t* liveList = nullptr;   // k_sieve's list of live bricks (one word per brick of the range)
+    size_t capLive = 0;
     uint32_t pShardCap = 0;
     float lastCs = 0.0f;            // the cell size of the last enqueued run
     uint64_t* scanStatus = nullptr; // 2 x kScanMaxBlocks look-back words (alternating runs)

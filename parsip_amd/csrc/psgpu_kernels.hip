@@ -30,6 +30,62 @@ __global__ void __launch_bounds__(256) k_precheck(Params p) {
     PSGPU_STAMPED(0, item_, precheck_body<InterpEval>(p, lds));
 }
 
+// k_sieve (PSGPU_OPT_SIEVE), ahead of S1: one lane per 2x2x2 brick of MPUs of the range.  A brick
+// over whose S1 corner box (brick_box) every primitive of the model's root-zero set is culled
+// reads +0 at all 64 corners, so none of its MPUs passes S1 (f > 0 fails): the lane writes what
+// its S1 wave would have (passed 0, counts 0) and no wave is spent on it.  The other bricks go on
+// the live list (one returning atomic per wave), which S1's waves then take in list order.  No
+// tree code: the same kernel serves the interpreter and every generated module.
+__global__ void __launch_bounds__(256) k_sieve(Params p) {
+    const int lane = lane_id();
+    const uint32_t bzN = p.brickDims[2], byN = p.brickDims[1];
+    const uint32_t nBricks = p.brickDims[0] * byN * bzN;
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    const bool have = b < nBricks;
+    uint32_t jk, bk;
+    const uint32_t bi = p.brickI0 + div_by(have ? b : 0u, byN * bzN, p.brickMagic[1], &jk);
+    const uint32_t bj = div_by(jk, bzN, p.brickMagic[0], &bk);
+    float blo[3], bhi[3], c[3] = {0.0f, 0.0f, 0.0f}, h = 0.0f;
+    brick_box(p.lo, p.side, p.dims, bi, bj, bk, blo, bhi);
+    const bool finite = cull_box(blo[0], blo[1], blo[2], bhi[0], bhi[1], bhi[2], c, &h);
+    ModelPtr M = as_const(p.model);
+    const uint64_t need[2] = {M->rootZero[0], M->rootZero[1]};
+    bool dead = have && finite && M->rootZeroValid != 0u;
+    for (uint32_t i = 0; i < 128u; ++i) {  // uniform: the segments come by scalar loads
+        if (!((need[i >> 6] >> (i & 63u)) & 1ull)) continue;
+        dead = dead && cull_one(load_cullseg(M, (int)i), c[0], c[1], c[2], h);
+    }
+    // the brick's MPUs in the range (precheck_body's `valid`); a brick without any needs no wave
+    uint32_t slotOf[8];
+    uint32_t validMask = 0u;
+#pragma unroll
+    for (uint32_t g = 0; g < 8u; ++g) {
+        const uint32_t mi = 2u * bi + ((g >> 2) & 1u), mj = 2u * bj + ((g >> 1) & 1u), mk = 2u * bk + (g & 1u);
+        const uint32_t mg = (mi * p.dims[1] + mj) * p.dims[2] + mk;
+        const bool valid = have && mi < p.dims[0] && mj < p.dims[1] && mk < p.dims[2] && mg >= p.mpuBegin &&
+                           mg - p.mpuBegin < p.mpuCount;
+        slotOf[g] = mg - p.mpuBegin;
+        validMask |= (valid ? 1u : 0u) << g;
+    }
+    if (dead) {
+#pragma unroll
+        for (uint32_t g = 0; g < 8u; ++g)
+            if ((validMask >> g) & 1u) {
+                p.passed[slotOf[g]] = 0;
+                p.counts[slotOf[g]] = 0ull;
+            }
+    }
+    const bool live = have && !dead && validMask != 0u;
+    const uint64_t bal = ballot(live);
+    if (bal == 0ull) return;
+    uint32_t base = 0u;
+    if (lane == __builtin_ctzll(bal)) base = atomicAdd(&p.ctr->liveBricks, (uint32_t)__popcll(bal));
+    base = lane_value(base, __builtin_ctzll(bal));
+    if (live)
+        p.liveList[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] =
+            (uint64_t)bi | ((uint64_t)bj << 21) | ((uint64_t)bk << 42);
+}
+
 __global__ void __launch_bounds__(256) k_mpu(Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     PSGPU_STAMPED(1, item_, mpu_body<InterpEval>(p, smem, &item_));
@@ -151,6 +207,11 @@ size_t precheck_lds_bytes(uint32_t slots) { return 4 * ((size_t)slots * 64 * 4);
 
 hipError_t launch_precheck(const Params& p, hipStream_t s) {
     hipLaunchKernelGGL(k_precheck, dim3(p.preBlocks), dim3(256), precheck_lds_bytes(p.slotsPerLane), s, p);
+    return hipGetLastError();
+}
+hipError_t launch_sieve(const Params& p, hipStream_t s) {
+    const uint32_t bricks = p.brickDims[0] * p.brickDims[1] * p.brickDims[2];
+    hipLaunchKernelGGL(k_sieve, dim3((bricks + 255u) / 256u), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 hipError_t launch_mpu(const Params& p, hipStream_t s) {

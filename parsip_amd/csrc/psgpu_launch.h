@@ -12,6 +12,7 @@ size_t mpu_lds_bytes(uint32_t slots);
 size_t walk_lds_bytes(uint32_t slots);
 size_t precheck_lds_bytes(uint32_t slots);
 hipError_t launch_precheck(const Params& p, hipStream_t s);
+hipError_t launch_sieve(const Params& p, hipStream_t s);  // k_sieve: one lane per brick of the range
 hipError_t launch_mpu(const Params& p, hipStream_t s);
 hipError_t launch_vertex(const Params& p, hipStream_t s, uint32_t blocks);
 hipError_t launch_finish(const Params& p, hipStream_t s, uint32_t blocks, int vpw);  // 64, 32 or 16 vertices per wave

@@ -34,8 +34,10 @@ typedef long long int64_t;
 #endif
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 #define PSGPU_HD __host__ __device__
+#define PSGPU_HDI __host__ __device__ __forceinline__  // inlined into the kernels: no call, no call ABI's registers
 #else
 #define PSGPU_HD
+#define PSGPU_HDI inline
 #endif
 
 namespace psgpu {
@@ -170,6 +172,56 @@ struct CullSeg {         // 48 B: three 16-B loads per lane
 };
 static_assert(sizeof(CullSeg) == 48, "CullSeg size");
 
+// sqrt of the culling tests: the device's v_sqrt_f32, the host's sqrtf (a plain C++ program
+// compiles these tests too: tests/cpp/sieve_check.cpp)
+PSGPU_HDI float cull_sqrt(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return __builtin_sqrtf(x);
+#endif
+}
+
+// Centre c and half-diagonal h (grown by its rounding) of the box [x0, x1] x [y0, y1] x [z0, z1]
+// for cull_one; false for a box that is not finite (a NaN compares false): nothing is culled.
+PSGPU_HDI bool cull_box(float x0, float y0, float z0, float x1, float y1, float z1, float c[3], float* h) {
+    if (!(x1 - x0 < 1e30f && y1 - y0 < 1e30f && z1 - z0 < 1e30f)) return false;
+    c[0] = 0.5f * (x0 + x1);
+    c[1] = 0.5f * (y0 + y1);
+    c[2] = 0.5f * (z0 + z1);
+    const float hx = 0.5f * (x1 - x0), hy = 0.5f * (y1 - y0), hz = 0.5f * (z1 - z0);
+    *h = cull_sqrt(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-6f;
+    return true;
+}
+
+// Is the segment's primitive exactly +0 over the box (centre c, half-diagonal h)?
+PSGPU_HDI bool cull_one(const CullSeg& S, float cx, float cy, float cz, float h) {
+    const float dx = cx - S.a[0], dy = cy - S.a[1], dz = cz - S.a[2];
+    const float t = (dx * S.u[0] + dy * S.u[1] + dz * S.u[2]) * S.invUU;
+    const float lx = dx - t * S.u[0], ly = dy - t * S.u[1], lz = dz - t * S.u[2];
+    const float lineDist = cull_sqrt(lx * lx + ly * ly + lz * lz);
+    const float tc = __builtin_fminf(__builtin_fmaxf(t, S.tmin), S.tmax);
+    const float ex = dx - tc * S.u[0], ey = dy - tc * S.u[1], ez = dz - tc * S.u[2];
+    const float d = (cull_sqrt(ex * ex + ey * ey + ez * ez) - S.radius) - h;
+    return d > 0.0f && d * d >= 1.02f && (lineDist - h > S.axisClear);
+}
+
+// The S1 corner box of the 2x2x2 brick of MPUs (bi, bj, bk) (brick coordinates of the lattice),
+// from the expressions precheck_body evaluates: the low face is the origin lo + (float)i * side
+// of the brick's lowest MPU, the high face side + origin of its highest one, where an MPU past
+// the lattice's high face is clamped to the last one.  The same bits as the minimum and maximum
+// of the wave's 64 corners (both expressions are monotone in the MPU index).
+PSGPU_HDI void brick_box(const float lo[3], float side, const uint32_t dims[3], uint32_t bi, uint32_t bj,
+                               uint32_t bk, float blo[3], float bhi[3]) {
+    const uint32_t b[3] = {bi, bj, bk};
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t m0 = 2u * b[a], last = dims[a] - 1u;
+        const uint32_t i0 = m0 < last ? m0 : last, i1 = m0 + 1u < last ? m0 + 1u : last;
+        blo[a] = lo[a] + (float)i0 * side;
+        bhi[a] = side + (lo[a] + (float)i1 * side);
+    }
+}
+
 struct DevModel {
     uint32_t nInstr;
     uint32_t nSlots;
@@ -182,7 +234,62 @@ struct DevModel {
     DevPrim prims[128];
     CullSeg cull[128];
     float zeroCol[128][4];  // colour of op i when every field below it is +0 (see host)
+    uint64_t rootZero[2];   // the primitives that, all culled over a box, make the root exactly +0
+                            // there (zero_subtree_set of the root; k_sieve) ...
+    uint32_t rootZeroValid; // ... and whether there is such a set (else no brick is ever dead)
+    uint32_t pad2;
 };
+
+#ifndef __HIPCC_RTC__
+// The zero-subtree rule (host): can op `op`'s subtree be proven exactly +0 over a box from the
+// culling mask alone, and if so, which primitives must be culled for it (added to m)?  A culled
+// primitive is +0 at every point of the box; Blend / Union / Intersect / Dif / SmoothDif of two
+// +0 children are +0, and so is a warp of a +0 left child.  False when the subtree evaluates a
+// primitive no mask ever culls (a matrix, Disc, Ring, an unknown type) or an op outside those
+// types (Ricci, unknown ops).  One definition for the generated walks' skip flags (Gen::zero_set,
+// psgpu_jit.cpp) and the model's root-zero set (build_device_model).
+inline bool prim_maybe_culled(const DevPrim& P) {
+    return P.type == PSGPU_T_TRIANGLE ||
+           (!P.hasMatrix && (P.type == PSGPU_T_POINT || P.type == PSGPU_T_LINE || P.type == PSGPU_T_CYLINDER ||
+                             P.type == PSGPU_T_CUBE));
+}
+inline bool zero_subtree_set(const DevModel& M, int op, uint64_t m[2], int depth = 0) {
+    const Instr* I = nullptr;
+    for (uint32_t k = 0; k < M.nInstr && !I; ++k)
+        if (M.instr[k].kind == kOp && M.instr[k].idx == op) I = &M.instr[k];
+    if (!I || depth > 128) return false;
+    const int type = I->type, kind = I->childKind;
+    auto child = [&](bool isOp, int id) {
+        if (isOp) return zero_subtree_set(M, id, m, depth + 1);
+        if (id >= 128 || !prim_maybe_culled(M.prims[id])) return false;
+        m[id >> 6] |= 1ull << (id & 63);
+        return true;
+    };
+    if (type >= 14 && type <= 18) return child((kind & 2) != 0, I->L) && child((kind & 1) != 0, I->R);
+    if (type >= 22 && type <= 25) return child((kind & 2) != 0, I->L);
+    return false;
+}
+// The root's set: for a tree without ops (the sum of the primitives) every primitive.  A set
+// with a primitive whose segment never culls (radius +inf: not eligible, or past ctPrims) is
+// no use: not valid.
+inline bool root_zero_set(const DevModel& M, uint64_t m[2]) {
+    m[0] = m[1] = 0ull;
+    bool ok = true;
+    if (M.ctOps == 0) {
+        for (uint32_t k = 0; k < M.nInstr; ++k) {
+            const uint32_t id = M.instr[k].idx;
+            if (M.instr[k].kind != kSumPrim || id >= 128 || !prim_maybe_culled(M.prims[id])) return false;
+            m[id >> 6] |= 1ull << (id & 63);
+        }
+        ok = M.nInstr > 0;
+    } else {
+        ok = zero_subtree_set(M, 0, m);
+    }
+    for (int i = 0; ok && i < 128; ++i)
+        if (((m[i >> 6] >> (i & 63)) & 1ull) && !(M.cull[i].radius < __builtin_inff())) ok = false;
+    return ok;
+}
+#endif
 
 // Compact-mesh work records written by the MPU kernel.
 // A vertex record in two arrays, so that each kernel moves only what it uses: k_mpu writes
@@ -231,7 +338,8 @@ struct DevCounters {
                              // k_precheck, never copied from the device counters by k_surface
     uint32_t epoch;          // run sequence number: the previous run's last kernel sets it to its own
                              // + 1 when it resets this set; k_front tags its queue entries with it + 1
-    uint32_t pad[27];
+    uint32_t liveBricks;     // k_sieve: bricks appended to the live list (Params::liveList)
+    uint32_t pad[26];
     ShardCtr shard[kShards];
 };
 
@@ -257,6 +365,12 @@ struct Params {
     uint32_t brickDims[3];  // bricks of the range along x, y, z
     uint32_t brickStride;   // wave W takes brick (W * brickStride) mod bricks (coprime: a
                             // permutation that spreads the surface's heavy bricks over the CUs)
+    // (the next three lie in one aligned 16 bytes: S1 reads them in its first instructions, and
+    // a load that also covered a word needed after the walk would hold registers across it)
+    uint32_t sieve;         // k_sieve ran ahead of S1: S1 wave slot W takes entry W of liveList
+    uint64_t* liveList;     // k_sieve: the bricks some primitive reaches, bi | bj << 21 | bk << 42
+                            // (lattice brick coordinates), ctr->liveBricks of them, in any order
+    uint32_t brickMagic[2]; // floor((2^32 - 1) / d) for d = brickDims[2], brickDims[1] * brickDims[2]
     uint32_t* pq;           // kShards queues of pShardCap S1 survivors (global MPU ids)
     uint64_t* pqMask;       // per queue entry: the MPU box's culling mask (2 words) and its op-inside
                             // mask (2 words, op_inside_box), by k_precheck
@@ -300,5 +414,8 @@ struct Params {
     uint32_t slotsPerLane;  // value slots (x4 floats in colour mode)
     uint32_t debug;         // ablation switches for profiling (0 in production)
 };
+
+static_assert(__builtin_offsetof(Params, liveList) % 16 == 0 && __builtin_offsetof(Params, pq) % 16 == 0,
+              "liveList and brickMagic fill one aligned 16 bytes");
 
 }  // namespace psgpu

@@ -27,6 +27,8 @@ struct LaunchOptions {
     int treeSplit = 0;   // PSGPU_OPT_TREE_SPLIT: 1 k_precheck / k_mpu walk the root's two subtrees in two waves
     int fusedSurface = 2;  // PSGPU_OPT_FUSED_SURFACE: k_vertex + k_finish in one launch (k_surface)
     int front = 2;         // PSGPU_OPT_FRONT: k_precheck + k_mpu in one launch (k_front)
+    int sieve = 0;         // PSGPU_OPT_SIEVE: k_sieve ahead of S1: 0 never (default: measured slower, DESIGN.md §4
+                           // "Round 12"), 1 whenever it applies, 2 unless the run is alone
     uint32_t splitMaxQueued = 1024;  // PSGPU_OPT_SPLIT_MAX_QUEUED: tree split 2 applies up to this many S2 MPUs
                                      // (psgpu_create: 4 per CU; C3's 1/8 shares queue ~800, 1/4 ~1,600)
     int gridFit = 1;       // k_vertex / k_finish grids sized from the last run's vertices, capped
@@ -57,6 +59,7 @@ struct PlanInput {
     bool jit, hasPrecheckS, hasSurface, hasSurfaceW, hasFront, hasFrontS;
     bool separate;   // finish re-runs a run whose in-kernel wait gave up: the separate kernels
     bool shortGrid;  // test hook (debug bit 20): a k_mpu grid that falls short (finish re-runs)
+    bool sievable = false;  // culling is on and the model has a root-zero set (k_sieve can prove bricks dead)
 };
 
 struct LaunchPlan {
@@ -70,8 +73,9 @@ struct LaunchPlan {
     uint32_t preBlocks, mpuBlocks, fqCap, scanChunks, scanBlocks;  // Params' fields of these names
     uint32_t gridVertex, gridFinish;  // the separate kernels' grids (0 with k_surface)
     uint32_t gridSurface;             // k_surface's grid (0 without)
+    uint32_t sieve;                   // 1: k_sieve runs ahead of S1, whose waves take its live list
 };
-static_assert(sizeof(LaunchPlan) == 4 + 11 * sizeof(uint32_t), "no padding: plans are compared with memcmp");
+static_assert(sizeof(LaunchPlan) == 4 + 12 * sizeof(uint32_t), "no padding: plans are compared with memcmp");
 
 // k_front sub-queue capacity for a k_precheck grid of `blocks` blocks of `mpb` bricks: every
 // 8th block's bricks x 8 MPUs
@@ -101,6 +105,13 @@ inline LaunchPlan plan_launch(const PlanInput& in) {
     pl.front = in.jit && o.front != 0 && !in.separate && !in.crowded && !in.mpuTicks &&
                (pl.split ? in.hasFrontS : in.hasFront) &&
                (o.front == 1 || (in.bricks + pl.mpb - 1) / pl.mpb <= 8u * cus);
+
+    // k_sieve ahead of S1 (no S1 wave for a brick no primitive reaches): where it can prove
+    // anything (sievable), never with per-MPU ticks (a dead brick's MPUs have no S1 wave to time);
+    // 2: not for a run alone on the device, whose span is its heaviest S1 waves and which
+    // would only pay the extra kernel boundary.  The S1 grid keeps its size: the waves past the
+    // list exit at once.
+    pl.sieve = in.sievable && !in.mpuTicks && (o.sieve == 1 || (o.sieve == 2 && !in.alone)) ? 1u : 0u;
 
     pl.fqCap = front_sub_cap(pl.preBlocks, pl.mpb);
     if (pl.front) {

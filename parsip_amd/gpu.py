@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_tritable", "psgpu_version", "psgpu_create", "psgpu_destroy", "psgpu_device_count",
     "psgpu_set_model", "psgpu_polygonize", "psgpu_finish", "psgpu_mesh_device", "psgpu_download_mesh",
     "psgpu_download_stats", "psgpu_export_polympus", "psgpu_polygonize_mpus", "psgpu_last_kernel_times",
-    "psgpu_field_values", "psgpu_set_option", "psgpu_jit_active", "psgpu_jit_source", "psgpu_jit_compile",
+    "psgpu_field_values", "psgpu_set_option", "psgpu_jit_active", "psgpu_jit_source", "psgpu_jit_compile", "psgpu_model_image",
     "psgpu_jit_pending", "psgpu_jit_wait", "psgpu_jit_tier", "psgpu_mpu_costs", "psgpu_split_costs",
     "psgpu_group_create", "psgpu_group_destroy", "psgpu_group_size", "psgpu_group_context",
     "psgpu_group_set_option", "psgpu_group_set_model", "psgpu_group_jit_wait", "psgpu_group_set_split",
@@ -76,7 +76,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
-    "psgpu_vertex_queue", "psgpu_mpu_masks",
+    "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks",
     "psgpu_group_weld", "psgpu_group_weld_device", "psgpu_group_download_weld", "psgpu_group_weld_times",
 ]
 
@@ -101,7 +101,8 @@ OPT_MPU_TICKS = 19
 OPT_FUSED_SURFACE = 21
 OPT_FRONT = 22
 OPT_OP_INSIDE = 23
-LAUNCH_TREE_SPLIT, LAUNCH_SURFACE, LAUNCH_FRONT, LAUNCH_RERUN = 1, 2, 4, 8  # PsMeshInfo.launchFlags
+OPT_SIEVE = 24
+LAUNCH_TREE_SPLIT, LAUNCH_SURFACE, LAUNCH_FRONT, LAUNCH_RERUN, LAUNCH_SIEVE = 1, 2, 4, 8, 16  # PsMeshInfo.launchFlags
 DEBUG_SURFACE_LATE_SCAN = 1 << 25  # test hooks of the in-kernel waits (OPT_DEBUG bits, one run each)
 DEBUG_LOOKBACK_TIMEOUT = 1 << 26
 DEBUG_FRONT_LATE_S1 = 1 << 27
@@ -158,6 +159,7 @@ def load(build_if_missing: bool = True):
         "psgpu_jit_tier": ([vp], i32),
         "psgpu_jit_source": ([vp, ctypes.c_char_p, ctypes.c_size_t], i32),
         "psgpu_jit_compile": ([vp, vp, vp, i32, ctypes.c_char_p, ctypes.c_size_t], ctypes.c_long),
+        "psgpu_model_image": ([vp, vp, vp, vp, ctypes.c_size_t], ctypes.c_long),
         "psgpu_mpu_costs": ([vp, vp], i32),
         "psgpu_download_stamps": ([vp, vp, ctypes.POINTER(u32)], i32),
         "psgpu_download_spans": ([vp, vp, ctypes.POINTER(u32)], i32),
@@ -194,6 +196,7 @@ def load(build_if_missing: bool = True):
         "psgpu_group_weld_times": ([vp, vp, i32, vp], i32),
         "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
         "psgpu_mpu_masks": ([vp, vp, vp, u32], i32),
+        "psgpu_live_bricks": ([vp, vp, u32, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -243,6 +246,18 @@ def jit_compile(model: soa.Model, mode: int = 1) -> int:
     if n < 0:
         raise PsgpuError(n, "psgpu_jit_compile: " + log.value.decode(errors="replace"))
     return n
+
+
+def model_image(model) -> bytes:
+    """Host-only: the device image of a model (psgpu::DevModel) as the kernels read it."""
+    L = load()
+    n = L.psgpu_model_image(*model.ptrs(), None, 0)
+    if n < 0:
+        raise PsgpuError(n, "psgpu_model_image")
+    buf = ctypes.create_string_buffer(n)
+    if L.psgpu_model_image(*model.ptrs(), buf, n) != n:
+        raise PsgpuError(n, "psgpu_model_image")
+    return buf.raw
 
 
 def device_count() -> int:
@@ -439,6 +454,19 @@ class Polygonizer:
         _check(self._L.psgpu_mpu_masks(self._ctx, queued.ctypes.data, masks.ctypes.data, len(queued)),
                "psgpu_mpu_masks")
         return queued[:info.ctMPUs].astype(bool), masks[:info.ctMPUs]
+
+    def live_bricks(self) -> np.ndarray:
+        """Debug export of the finished run's live bricks: an (n, 3) uint32 array, in k_sieve's
+        list order (any order), of the lattice brick coordinates (MPU coordinates // 2) of the
+        2x2x2 bricks of MPUs that S1 waves took; empty when the run took no sieve
+        (LAUNCH_SIEVE)."""
+        self.finish()
+        ct = ctypes.c_uint32()
+        _check(self._L.psgpu_live_bricks(self._ctx, None, 0, ctypes.byref(ct)), "psgpu_live_bricks")
+        out = np.zeros((max(ct.value, 1), 3), np.uint32)
+        _check(self._L.psgpu_live_bricks(self._ctx, out.ctypes.data, len(out), ctypes.byref(ct)),
+               "psgpu_live_bricks")
+        return out[:ct.value]
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info = self.finish()
