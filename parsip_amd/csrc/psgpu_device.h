@@ -752,17 +752,7 @@ __device__ __forceinline__ void mpu_ticks_s2(const Params& p, uint32_t m) {
     }
 
 // ---------------------------------------------------------------------------
-// Exact m / d from a multiply-high by floor((2^32 - 1) / d): the estimate never exceeds the
-// quotient and falls short of it by at most 2.
-__device__ __forceinline__ uint32_t div_by(uint32_t m, uint32_t d, uint32_t magic, uint32_t* rem) {
-    uint32_t q = __umulhi(m, magic);
-    uint32_t r = m - q * d;
-    if (r >= d) { ++q; r -= d; }
-    if (r >= d) { ++q; r -= d; }
-    *rem = r;
-    return q;
-}
-
+// (div_by, the exact m / d of the decodes below: psgpu_model.h)
 __device__ __forceinline__ void mpu_origin(const Params& p, uint32_t m, float o[3]) {
     uint32_t k, jk;
     const uint32_t i = div_by(m, p.dims[2] * p.dims[1], p.divMagic[1], &jk);

@@ -222,6 +222,21 @@ PSGPU_HDI void brick_box(const float lo[3], float side, const uint32_t dims[3], 
     }
 }
 
+// Exact m / d from a multiply-high by magic = floor((2^32 - 1) / d): the estimate never exceeds
+// the quotient and falls short of it by at most 2 (tests/cpp/divby_check.cpp).
+PSGPU_HDI uint32_t div_by(uint32_t m, uint32_t d, uint32_t magic, uint32_t* rem) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t q = __umulhi(m, magic);
+#else
+    uint32_t q = (uint32_t)(((uint64_t)m * magic) >> 32);
+#endif
+    uint32_t r = m - q * d;
+    if (r >= d) { ++q; r -= d; }
+    if (r >= d) { ++q; r -= d; }
+    *rem = r;
+    return q;
+}
+
 struct DevModel {
     uint32_t nInstr;
     uint32_t nSlots;

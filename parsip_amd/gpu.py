@@ -109,6 +109,7 @@ DEBUG_FRONT_LATE_S1 = 1 << 27
 DEBUG_EPOCH_NEAR_WRAP = 1 << 28  # test hook: the next run starts 3 runs short of the epoch's wrap
 DEBUG_EXPORT_POISON = 1 << 23  # test hooks of the blocking export (OPT_DEBUG bits)
 DEBUG_EXPORT_STRAGGLER = 1 << 24
+DEBUG_BRICK_SPREAD = 1 << 14  # k_precheck's wave W takes brick (W * brickStride) mod bricks (bench.py --debug)
 JIT_INTERP, JIT_STRUCTURE, JIT_BAKED, JIT_TIERED = 0, 1, 2, 3  # OPT_JIT values
 STAMP_KERNELS = ("k_precheck", "k_mpu", "k_vertex", "k_finish")
 GROUP_OPT_BALANCE = 100

@@ -12,6 +12,8 @@ the reference is absent.
   polygonizer's vertex stage calls it).  The trees hold no Disc, Ring or RicciBlend, so
   every recorded bit but the normals' is plain IEEE arithmetic and independent of the host
   CPU's rsqrtps / rcpps; normals are compared within 2e-3.
+* the same for the trees of BOX_FIXTURES, each in a box whose MPU lattice has three pairwise
+  distinct dims (``box<dims>_tree<seed>.npz``; every other fixture's lattice is a cube).
 * ``index.json``: the node types in each tree and its sizes.
 * ``deviation.json``: the measured distance between the IEEE oracle and the reference on
   trees with Disc / Ring / RicciBlend, and between the two PrepareBBoxes
@@ -33,6 +35,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 
+import aniso_util as au  # noqa: E402
 import psoracle  # noqa: E402
 import psref  # noqa: E402
 import reference_util as ru  # noqa: E402
@@ -43,6 +46,17 @@ OUT = ru.GOLDEN_REF
 FIXTURE_SEEDS = (3, 7, 29, 113, 142, 186, 193, 383)  # what --search printed
 MAX_MPUS, MIN_V, MAX_V, N_QUADS = 512, 200, 1500, 256
 N_MAX = 8  # small trees: each node weighs on its mesh
+# (seed, dims): trees of the same family in boxes that are no cubes (tests/aniso_util.box_for
+# around the origin), the three rotations of one shape -- chosen by hand among the seeds below
+# 120 for MIN_V to MAX_V vertices and surface MPUs at three or more places along every axis
+BOX_FIXTURES = ((43, (8, 5, 3)), (9, (5, 3, 8)), (53, (3, 8, 5)))
+
+
+def box_case(seed, dims):
+    model, cs = ru.exact_case(seed, MAX_MPUS, N_MAX)
+    model = au.boxed(model, *au.box_for(dims, (0.0, 0.0, 0.0), cs))
+    assert soa.mpu_dims(cs, *model.bbox) == dims
+    return model, cs
 
 
 def wanted():
@@ -113,6 +127,10 @@ def main():
     for s in FIXTURE_SEEDS:
         model, cs = ru.exact_case(s, MAX_MPUS, N_MAX)
         index["fixtures"][f"tree{s}"] = dict(record(f"tree{s}", model, cs), seed=s)
+    for s, dims in BOX_FIXTURES:
+        model, cs = box_case(s, dims)
+        name = "box" + "x".join(str(d) for d in dims) + f"_tree{s}"
+        index["fixtures"][name] = dict(record(name, model, cs), seed=s, dims=list(dims))
     with open(os.path.join(OUT, "index.json"), "w") as f:
         json.dump(index, f, indent=1)
     dev = {"generator": "tests/golden/make_reference_goldens.py (tests/reference_util.measure_deviation, measure_boxes)",

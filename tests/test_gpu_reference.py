@@ -1,6 +1,7 @@
 """The HIP path against the reference's own recorded output (tests/golden/reference/*.npz, written
 by tests/golden/make_reference_goldens.py from the compiled PS::SIMDPOLY), not against the
-oracle: C1 and eight trees without Disc / Ring / RicciBlend, where every bit the reference
+oracle: C1 and eight trees without Disc / Ring / RicciBlend in cubes and three more in boxes whose
+lattices are (8,5,3), (5,3,8) and (3,8,5), where every bit the reference
 computes is plain IEEE arithmetic -- per-MPU ctFieldEvals / V / T, offsets, MPU-local
 triangles, positions and colours bit-exact; normals within 2e-3 (the reference normalises with
 rsqrtps); fieldValue and fieldValueAndColor at recorded points bit-exact.  Interpreter and

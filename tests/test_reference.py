@@ -191,12 +191,18 @@ def test_prepare_bboxes_against_reference(ref, oracle):
 # ---------------------------------------------------------------------------
 # recorded reference outputs: run everywhere, no reference binary needed
 def test_recorded_fixture_set():
-    """C1 and six to eight approximation-free trees; together every primitive and operator of
-    2b, all four warps, matrices on and off; sizes within what a committed fixture may take."""
+    """C1 and six to eight approximation-free trees in cubes; together every primitive and operator
+    of 2b, all four warps, matrices on and off; sizes within what a committed fixture may take.
+    Then three more such trees in boxes whose lattices have three pairwise distinct dims, the three
+    rotations of one shape."""
     with open(os.path.join(ru.GOLDEN_REF, "index.json")) as f:
         idx = json.load(f)["fixtures"]
     names = ru.fixture_names()
-    assert names[0] == "C1" and 6 <= len(names) - 1 <= 8
+    boxes = [n for n in names if "dims" in idx[n]]
+    assert names[0] == "C1" and 6 <= len(names) - len(boxes) - 1 <= 8 and names[-len(boxes):] == boxes
+    shapes = [tuple(idx[n]["dims"]) for n in boxes]
+    assert len(boxes) == 3 and all(len(set(s)) == 3 for s in shapes)
+    assert {shapes[0], shapes[0][1:] + shapes[0][:1], shapes[0][2:] + shapes[0][:2]} == set(shapes)
     prims, ops, mats, total = set(), set(), set(), 0
     for n in names:
         model, cs, d, mesh = ru.load_fixture(n)
@@ -204,10 +210,14 @@ def test_recorded_fixture_set():
         assert [ru.TYPE_NAMES[t] for t in p] == idx[n]["prims"] and [ru.TYPE_NAMES[t] for t in o] == idx[n]["ops"]
         assert not ru.has_approx(model)
         assert len(mesh.stats) == soa.count_mpus(cs, *model.bbox) <= 512 and len(mesh.pos) >= 200
+        dims = soa.mpu_dims(cs, *model.bbox)
+        assert (dims == tuple(idx[n]["dims"])) if n in boxes else (len(set(dims)) == 1), (n, dims)
         assert len(d["quad_field"]) == 4 * 256 and len(d["point_field"]) == 256
         size = os.path.getsize(os.path.join(ru.GOLDEN_REF, n + ".npz"))
         assert size <= 100_000, (n, size)
         total += size
+        if n in boxes:
+            continue  # the coverage asked below is the cubes' own
         prims |= set(p)
         ops |= set(o)
         mats.add(bool(model.prims["idxMatrix"][0, :model.ct_prims].any()))

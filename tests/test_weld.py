@@ -27,11 +27,12 @@ def lattice_weld(oracle, name):
     return _CACHE[key]
 
 
-@pytest.mark.parametrize("name,vertices,open_bits", [("rand3_0.071", 3334, 1276), ("rand4_0.123457", 1654, 588)])
+@pytest.mark.parametrize("name,vertices,open_bits", [("rand3_0.071", 3334, 1276), ("rand4_0.123457", 1654, 588),
+                                                     ("rand3_0.071_box_6x7x5", 3378, 1032)])
 def test_closed_surface_welds_watertight(oracle, name, vertices, open_bits):
     """A closed surface inside the box at an ordinary cell size: the lattice-edge weld leaves no
     open edge (every undirected edge in exactly two triangles), the weld by position bits
-    leaves hundreds."""
+    leaves hundreds.  The third case is a (6, 7, 5) lattice, the others are cubes."""
     gold = golden_counts()[name]
     _, _, _, m, _ = oracle_case(oracle, name)
     w, _ = lattice_weld(oracle, name)

@@ -18,7 +18,11 @@ CASES = {
     "rand4_0.123457": ("random", 4, 0.123457, None),
     "rand1_0.13": ("random", 1, 0.13, None),
     "rand3_0.071_mpus_243_486": ("random", 3, 0.071, (243, 486)),
+    # the same closed surface in a box that is no cube: a (6, 7, 5) lattice (tests/aniso_util.py)
+    "rand3_0.071_box_6x7x5": ("boxed", 3, 0.071, None),
 }
+BOXED_NAME = "rand3_0.071_box_6x7x5"
+BOX_LO, BOX_HI = (-1.35, -1.10, -1.03), (1.17, 1.95, 1.02)
 
 
 def make_case(name):
@@ -28,6 +32,9 @@ def make_case(name):
         model, cs, _ = synth.make_config(which)
     else:
         model = synth.random_model(which, 6)
+    if kind == "boxed":
+        model.prims["bboxLo"][0] = BOX_LO
+        model.prims["bboxHi"][0] = BOX_HI
     return model, cs, rng or (0, None)
 
 
