@@ -764,6 +764,162 @@ __device__ __forceinline__ void mpu_origin(const Params& p, uint32_t m, float o[
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return lane_value(wave_incl_scan(v), 63); }
 
+// ---------------------------------------------------------------------------
+// S1/S2 stages: what k_precheck, k_mpu and k_front are built from (DESIGN.md §3 "S1/S2 stages").
+// Each exists once; precheck_body and mpu_body are their stage lists.  Every barrier and every
+// early return between two barriers is written in the bodies, with one exception that says so in
+// its name and comment: block_s2_inside_bits.
+
+// k_front's tag of this run's queue entries: never 0 (the ready words start zeroed, and are
+// zeroed again whenever the counter sets restart from epoch 0)
+__device__ __forceinline__ uint32_t front_tag(const Params& p) { return p.ctr->epoch + 1u; }
+
+// Phase word 7 of the wave's stamp row (`on`: the kernel's phase-stamp debug bit is set): its live
+// primitives and, above them, what the kernel adds (S1: the lanes that passed << 16; k_mpu's
+// measurement build: V << 16 | T << 32)
+__device__ __forceinline__ void stamp_live_word(const Params& p, bool on, const CullMask& cm, uint64_t above) {
+    if (on && p.stamps && lane_id() == 0) {
+        const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if (w < p.stampCap)
+            p.stamps[3 * (size_t)kNumStampKernels * p.stampCap + 8 * (size_t)w + 7] =
+                (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | above;
+    }
+}
+
+// Field bounds (see prim_bound): lane c of an MPU bounds the 4x4x4 corners [4X, 4X+3] x
+// [4Y, 4Y+3] x [4Z, 4Z+3] of its S2 cache (its z range is exactly one S2 quad), at the S2
+// coordinates (block_s2_inside_bits): o + (float)index * cs.  The one definition of the
+// half-diagonal's slack.
+__device__ __forceinline__ BoundBox octant_box(const Params& p, const float o[3], int c) {
+    BoundBox B;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        B.xs[i] = o[0] + (float)(4 * (c & 1) + i) * p.cs;
+        B.ys[i] = o[1] + (float)(4 * ((c >> 1) & 1) + i) * p.cs;
+        B.zs[i] = o[2] + (float)(4 * (c >> 2) + i) * p.cs;
+    }
+    const float hx = 0.5f * (B.xs[3] - B.xs[0]), hy = 0.5f * (B.ys[3] - B.ys[0]), hz = 0.5f * (B.zs[3] - B.zs[0]);
+    B.cx = 0.5f * (B.xs[0] + B.xs[3]);
+    B.cy = 0.5f * (B.ys[0] + B.ys[3]);
+    B.cz = 0.5f * (B.zs[0] + B.zs[3]);
+    B.h = __builtin_amdgcn_sqrtf(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-4f;
+    return B;
+}
+
+// The lanes' octant intervals -> bit g: MPU g passed S1 (flags8) and all 8 of its octants are
+// proven outside (hi < 0.5) or all 8 inside (lo >= 0.5): no surface, 0 V / 0 T without S2
+__device__ __forceinline__ uint32_t proven_mask(bool ok, float lo, float hi, uint32_t flags8) {
+    const uint64_t bOut = ballot(ok && hi < 0.5f), bIn = ballot(ok && lo >= 0.5f);
+    uint32_t proven8 = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const bool all = ((bOut >> (8 * q)) & 0xffull) == 0xffull || ((bIn >> (8 * q)) & 0xffull) == 0xffull;
+        proven8 |= (all ? 1u : 0u) << q;
+    }
+    return proven8 & flags8;
+}
+
+// Culling mask of each queued MPU (queue8; lane g < 8 holds MPU g's id in mOf), from this
+// wave's culling segments (already in registers): its box grown by the normal delta, for
+// k_vertex / k_finish (mpuMasks) and, with the queue entry, for S2 (k_mpu loads no culling
+// data).  The grown box contains the S2 box, so its mask is conservative there too; one mask
+// per MPU instead of two (the boxes differ by 0.001: the masks are the same but for primitives
+// grazing the box).  Beside it the MPU's op-inside mask (op_inside_box; its own margin, no
+// culling slack), lane-parallel over the ops as the culling mask is over the primitives: lane i
+// holds the boxes of ops i and 64 + i, one ballot per word.  PSGPU_OPT_OP_INSIDE 0: zero masks.
+// Returns to lane q < 8 MPU q's masks, for its queue entry (zero without culling).
+__device__ __forceinline__ CullMask queue_masks(const Params& p, const CullLanes& cl, const float o[3],
+                                                uint32_t queue8, uint32_t mOf, int lane) {
+    CullMask mine{0ull, 0ull};
+    if (!p.cull) return mine;
+    const float eg = 7.0f * p.cs + 0.001f;
+    ModelPtr Mo = as_const(p.model);
+    const uint32_t nOps = p.opInside ? Mo->ctOps : 0u;
+    float bl[2][3], bh[2][3];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t k = 64u * h + (uint32_t)lane;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {  // past ctOps: an empty box, inside of nothing
+            bl[h][a] = k < nOps ? p.model->ops[k].lo[a] : 1.0f;
+            bh[h][a] = k < nOps ? p.model->ops[k].hi[a] : -1.0f;
+        }
+    }
+    for (uint32_t qm = queue8; qm != 0u; qm &= qm - 1u) {
+        const int q = __builtin_ctz(qm);
+        const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[0]), 8 * q));
+        const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[1]), 8 * q));
+        const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[2]), 8 * q));
+        CullMask g = cull_mask_from(cl, ox, oy, oz, ox + eg, oy + eg, oz + eg);
+        if (nOps != 0u) g.inLo = ballot((uint32_t)lane < nOps && op_inside_box(bl[0], bh[0], ox, oy, oz, p.cs));
+        if (nOps > 64u)
+            g.inHi = ballot(64u + (uint32_t)lane < nOps && op_inside_box(bl[1], bh[1], ox, oy, oz, p.cs));
+        const uint32_t wq = lane_value(mOf, q) - p.mpuBegin;
+        if (lane == 0) {
+            p.mpuMasks[4 * wq] = g.lo;
+            p.mpuMasks[4 * wq + 1] = g.hi;
+            p.mpuMasks[4 * wq + 2] = g.inLo;
+            p.mpuMasks[4 * wq + 3] = g.inHi;
+        }
+        if (lane == q) mine = g;
+    }
+    return mine;
+}
+
+// A queued MPU as S1 hands it to S2: its global id in pq[slotq] and four mask words in
+// pqMask[4 * slotq ..] (the MPU box's culling mask and op-inside mask, from queue_masks; not
+// written and not read without culling).  Between launches (k_precheck, then k_mpu) plain
+// stores and loads.  Within k_front's one launch (FRONT; MI355X_MICROARCH.md hand-off table,
+// first row) S2 waves on other CUs read what S1 waves wrote: every store is write-through and
+// every load agent-scope (sc1 on both sides); once a wave's entries and masks have left it
+// (vmcnt(0)) each entry's ready word fqReady[slotq] takes the run's tag (publish), and an S2
+// wave reads an entry only after it saw the tag there (acquire_front).
+// The second op-inside word: S1 always writes it (zero for trees of at most 64 ops); the FRONT
+// load skips it for such trees, the plain load takes it always -- equal values either way.
+struct QueueEntry {
+    uint32_t m;
+    CullMask cm;
+
+    template <bool FRONT, class T>
+    static __device__ __forceinline__ void put(T* at, T v) {
+        if constexpr (FRONT) __hip_atomic_store(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *at = v;
+    }
+    template <bool FRONT, class T>
+    static __device__ __forceinline__ T get(T* at) {
+        if constexpr (FRONT) return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return *at;
+    }
+    template <bool FRONT>
+    __device__ __forceinline__ void store(const Params& p, uint32_t slotq) const {
+        put<FRONT>(&p.pq[slotq], m);
+        if (p.cull) {
+            put<FRONT>(&p.pqMask[4 * slotq], cm.lo);
+            put<FRONT>(&p.pqMask[4 * slotq + 1], cm.hi);
+            put<FRONT>(&p.pqMask[4 * slotq + 2], cm.inLo);
+            put<FRONT>(&p.pqMask[4 * slotq + 3], cm.inHi);
+        }
+    }
+    // FRONT only, by every lane of the wave after its stores; `mine`: this lane stored entry slotq
+    static __device__ __forceinline__ void publish(const Params& p, uint32_t slotq, bool mine) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (mine) put<true>(&p.fqReady[slotq], front_tag(p));
+    }
+    // wave-uniform: the id and the masks in SGPRs, so every per-primitive culling test and every
+    // skip of an op-box pruning test of the S2 walk is a scalar branch
+    template <bool FRONT>
+    static __device__ __forceinline__ QueueEntry load(const Params& p, ModelPtr M, uint32_t slotq) {
+        QueueEntry e{uniform(get<FRONT>(&p.pq[slotq])), CullMask{0ull, 0ull}};
+        if (p.cull) {
+            e.cm.lo = uniform64(get<FRONT>(&p.pqMask[4 * slotq]));
+            e.cm.hi = uniform64(get<FRONT>(&p.pqMask[4 * slotq + 1]));
+            e.cm.inLo = uniform64(get<FRONT>(&p.pqMask[4 * slotq + 2]));
+            if (!FRONT || M->ctOps > 64u) e.cm.inHi = uniform64(get<FRONT>(&p.pqMask[4 * slotq + 3]));
+        }
+        return e;
+    }
+};
+
 // S1: 8 corners per MPU, lanes 0-3 z = lo, lanes 4-7 z = lo + side; (x,y) lanes
 // (0,0),(1,0),(0,1),(1,1) (PS_Polygonizer.cpp:488-519).  One wavefront = one 2x2x2
 // brick of MPUs (lanes 8g..8g+7: MPU g = bx*4 + by*2 + bz), so the wave's culling box
@@ -776,10 +932,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return lane_value(wav
 // (combine / bound_combine): the same values, half the walk per wave -- for launches whose
 // span is the heaviest brick's walk (small rank shares, a single engine).  Every wave of the
 // block reaches both barriers; the second wave of a brick stops after them.
-// k_front's tag of this run's queue entries: never 0 (the ready words start zeroed, and are
-// zeroed again whenever the counter sets restart from epoch 0)
-__device__ __forceinline__ uint32_t front_tag(const Params& p) { return p.ctr->epoch + 1u; }
-
 template <class EV, int SPLIT = 1, bool FRONT = false>
 __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     const int wave = (int)uniform((uint32_t)wave_index());  // scalar: so are its brick slot and tree part
@@ -868,40 +1020,21 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     }
     const uint64_t bal = ballot(valid && f > 0.0f);
     phase_stamp(p, 1, 8192u);
-    if ((p.debug & 8192u) && p.stamps && lane == 0) {  // phase word 7: the wave's live primitives, S1 passes
-        const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (w < p.stampCap)
-            p.stamps[3 * (size_t)kNumStampKernels * p.stampCap + 8 * (size_t)w + 7] =
-                (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | ((uint64_t)__popcll(bal) << 16);
-    }
+    stamp_live_word(p, p.debug & 8192u, cm, (uint64_t)__popcll(bal) << 16);
     uint32_t flags8 = 0;  // bit g: MPU of lanes 8g..8g+7 passed
 #pragma unroll
     for (int q = 0; q < 8; ++q) flags8 |= (((bal >> (8 * q)) & 0xffull) != 0ull ? 1u : 0u) << q;
-    // Survivors proven empty by field bounds (see prim_bound): lane c of an MPU bounds
-    // the 4x4x4 corners [4X, 4X+3] x [4Y, 4Y+3] x [4Z, 4Z+3] of its S2 cache (its z range
-    // is exactly one S2 quad); the wave's culling box covers every MPU of the brick.
+    // survivors proven empty by field bounds; the wave's culling box covers every MPU of the brick
     uint32_t proven8 = 0;
-    uint64_t bOut = 0ull, bIn = 0ull;  // per lane (MPU g, octant c): proven all outside / all inside
+    float lo = 0.0f, hi = 0.0f;  // the lane's interval over its octant
+    bool ok = true;
     if ((p.debug & 1024u) && flags8 != 0u) __builtin_amdgcn_s_setprio(2);  // experiment: heavy waves first
     if constexpr (SPLIT == 2) {
         __shared__ float sLo[4][64], sHi[4][64];
         __shared__ uint32_t sOk[4][64];
         const bool doBound = p.bound && flags8 != 0u;  // the same for both waves of the brick
-        float lo = 0.0f, hi = 0.0f;
-        bool ok = true;
-        BoundBox B;
         if (doBound) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                B.xs[i] = o[0] + (float)(4 * (c & 1) + i) * p.cs;
-                B.ys[i] = o[1] + (float)(4 * ((c >> 1) & 1) + i) * p.cs;
-                B.zs[i] = o[2] + (float)(4 * (c >> 2) + i) * p.cs;
-            }
-            const float hx = 0.5f * (B.xs[3] - B.xs[0]), hy = 0.5f * (B.ys[3] - B.ys[0]), hz = 0.5f * (B.zs[3] - B.zs[0]);
-            B.cx = 0.5f * (B.xs[0] + B.xs[3]);
-            B.cy = 0.5f * (B.ys[0] + B.ys[3]);
-            B.cz = 0.5f * (B.zs[0] + B.zs[3]);
-            B.h = __builtin_amdgcn_sqrtf(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-4f;
+            const BoundBox B = octant_box(p, o, c);
             if (part == 0) ev.template bound_part<0>(B, cm, &lo, &hi, &ok);
             else ev.template bound_part<1>(B, cm, &lo, &hi, &ok);
         }
@@ -914,39 +1047,11 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
             const int r = slot * 2, l = slot * 2 + 1;
             ok = sOk[r][lane] != 0u && sOk[l][lane] != 0u;
             ev.bound_combine(sLo[r][lane], sHi[r][lane], sLo[l][lane], sHi[l][lane], cm, &lo, &hi);
-            bOut = ballot(ok && hi < 0.5f);
-            bIn = ballot(ok && lo >= 0.5f);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const bool all = ((bOut >> (8 * q)) & 0xffull) == 0xffull || ((bIn >> (8 * q)) & 0xffull) == 0xffull;
-                proven8 |= (all ? 1u : 0u) << q;
-            }
-            proven8 &= flags8;
+            proven8 = proven_mask(ok, lo, hi, flags8);
         }
     } else if (p.bound && flags8 != 0u) {
-        BoundBox B;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {  // the S2 coordinates (mpu_body): o + (float)index * cs
-            B.xs[i] = o[0] + (float)(4 * (c & 1) + i) * p.cs;
-            B.ys[i] = o[1] + (float)(4 * ((c >> 1) & 1) + i) * p.cs;
-            B.zs[i] = o[2] + (float)(4 * (c >> 2) + i) * p.cs;
-        }
-        const float hx = 0.5f * (B.xs[3] - B.xs[0]), hy = 0.5f * (B.ys[3] - B.ys[0]), hz = 0.5f * (B.zs[3] - B.zs[0]);
-        B.cx = 0.5f * (B.xs[0] + B.xs[3]);
-        B.cy = 0.5f * (B.ys[0] + B.ys[3]);
-        B.cz = 0.5f * (B.zs[0] + B.zs[3]);
-        B.h = __builtin_amdgcn_sqrtf(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-4f;
-        float lo = 0.0f, hi = 0.0f;
-        bool ok = true;
-        ev.bound(B, cm, &lo, &hi, &ok);
-        bOut = ballot(ok && hi < 0.5f);
-        bIn = ballot(ok && lo >= 0.5f);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const bool all = ((bOut >> (8 * q)) & 0xffull) == 0xffull || ((bIn >> (8 * q)) & 0xffull) == 0xffull;
-            proven8 |= (all ? 1u : 0u) << q;
-        }
-        proven8 &= flags8;
+        ev.bound(octant_box(p, o, c), cm, &lo, &hi, &ok);
+        proven8 = proven_mask(ok, lo, hi, flags8);
         phase_stamp(p, 2, 8192u);
     }
     const uint32_t queue8 = flags8 & ~proven8;
@@ -972,105 +1077,31 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     // made (their round trip overlaps the mask computation; verdict r05 item 4)
     uint32_t baseAtomic = 0;
     if (lane == 0) baseAtomic = atomicAdd(&p.ctr->shard[qsel].p, (uint32_t)__popc(queue8));
-    // Culling mask of each queued MPU, from this wave's culling segments (already in
-    // registers): its box grown by the normal delta, for k_vertex / k_finish (mpuMasks) and,
-    // with the queue entry, for S2 (k_mpu loads no culling data).  The grown box contains the
-    // S2 box, so its mask is conservative there too; one mask per MPU instead of two (the
-    // boxes differ by 0.001: the masks are the same but for primitives grazing the box).
-    // Beside it the MPU's op-inside mask (op_inside_box; its own margin, no culling slack),
-    // lane-parallel over the ops as the culling mask is over the primitives: lane i holds the
-    // boxes of ops i and 64 + i, one ballot per word.  PSGPU_OPT_OP_INSIDE 0: zero masks.
-    uint64_t mLo = 0ull, mHi = 0ull, iLo = 0ull, iHi = 0ull;  // lane q < 8: MPU q's masks, for its queue entry
-    if (p.cull) {
-        const float eg = 7.0f * p.cs + 0.001f;
-        ModelPtr Mo = as_const(p.model);
-        const uint32_t nOps = p.opInside ? Mo->ctOps : 0u;
-        float bl[2][3], bh[2][3];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t k = 64u * h + (uint32_t)lane;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {  // past ctOps: an empty box, inside of nothing
-                bl[h][a] = k < nOps ? p.model->ops[k].lo[a] : 1.0f;
-                bh[h][a] = k < nOps ? p.model->ops[k].hi[a] : -1.0f;
-            }
-        }
-        for (uint32_t qm = queue8; qm != 0u; qm &= qm - 1u) {
-            const int q = __builtin_ctz(qm);
-            const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[0]), 8 * q));
-            const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[1]), 8 * q));
-            const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o[2]), 8 * q));
-            CullMask g = cull_mask_from(cl, ox, oy, oz, ox + eg, oy + eg, oz + eg);
-            if (nOps != 0u) g.inLo = ballot((uint32_t)lane < nOps && op_inside_box(bl[0], bh[0], ox, oy, oz, p.cs));
-            if (nOps > 64u)
-                g.inHi = ballot(64u + (uint32_t)lane < nOps && op_inside_box(bl[1], bh[1], ox, oy, oz, p.cs));
-            const uint32_t wq = lane_value(mOf, q) - p.mpuBegin;
-            if (lane == 0) {
-                p.mpuMasks[4 * wq] = g.lo;
-                p.mpuMasks[4 * wq + 1] = g.hi;
-                p.mpuMasks[4 * wq + 2] = g.inLo;
-                p.mpuMasks[4 * wq + 3] = g.inHi;
-            }
-            if (lane == q) {
-                mLo = g.lo;
-                mHi = g.hi;
-                iLo = g.inLo;
-                iHi = g.inHi;
-            }
-        }
-    }
-    asm volatile("" : "+v"(baseAtomic) : "v"(mLo));  // the wait for the atomic goes here
+    const QueueEntry e{mOf, queue_masks(p, cl, o, queue8, mOf, lane)};  // lane q < 8: MPU q's entry
+    asm volatile("" : "+v"(baseAtomic) : "v"(e.cm.lo));  // the wait for the atomic goes here
     const uint32_t base = lane_value(baseAtomic, 0);
-    if (pass) {  // lane q < 8 writes MPU q's entry
-        const uint32_t slotq = qbase + base + (uint32_t)__popc(queue8 & ((1u << lane) - 1u));
-        if (FRONT) {  // read in this launch by S2 waves on other CUs: write-through (sc1)
-            __hip_atomic_store(&p.pq[slotq], mOf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (p.cull) {
-                __hip_atomic_store(&p.pqMask[4 * slotq], mLo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&p.pqMask[4 * slotq + 1], mHi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&p.pqMask[4 * slotq + 2], iLo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&p.pqMask[4 * slotq + 3], iHi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            p.pq[slotq] = mOf;
-            if (p.cull) {
-                p.pqMask[4 * slotq] = mLo;
-                p.pqMask[4 * slotq + 1] = mHi;
-                p.pqMask[4 * slotq + 2] = iLo;
-                p.pqMask[4 * slotq + 3] = iHi;
-            }
-        }
-    }
+    const uint32_t slotq = pass ? qbase + base + (uint32_t)__popc(queue8 & ((1u << lane) - 1u)) : 0u;
+    if (pass) e.template store<FRONT>(p, slotq);
     phase_stamp(p, 3, 8192u);
-    if constexpr (FRONT) {
-        // publish (MI355X_MICROARCH.md hand-off table, first row): the entries and masks were
-        // stored sc1; once they have left this wave (vmcnt(0)), each queued MPU's ready word
-        // takes the run's tag (sc1); S2 waves poll it with sc1 loads and then read the entry
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (pass) {
-            const uint32_t slotq = qbase + base + (uint32_t)__popc(queue8 & ((1u << lane) - 1u));
-            __hip_atomic_store(&p.fqReady[slotq], front_tag(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if constexpr (FRONT) QueueEntry::publish(p, slotq, pass);
 }
 
 #ifndef PSGPU_S2_N
 #define PSGPU_S2_N 8  // x-slices per walk: one walk per (y,z) needle shares each primitive's
                       // uniform work and (y,z) terms over its points
 #endif
-// LDS per k_mpu block: per MPU of the block (4, or 2 with the tree split): edgeVid[1536] u16
-// (passes 2-3) | cfg[344] u8 | vbase[344] u16 | tbase[344] u16 | the 8 inside-bit words of the
-// S2 cache | a spare word, qt (the tree split's triangle base); then per wave the
-// interpreter's value slots.  The S2 field values never leave registers: pass 1 needs
+// LDS per k_mpu block: one MpuLds per MPU of the block (4, or 2 with the tree split), then per
+// wave the interpreter's value slots.  The S2 field values never leave registers: pass 1 needs
 // only their inside bits (8 ballots, shared by the MPU's waves through LDS).
-constexpr int kLdsEdge = 0;
-constexpr int kLdsCfg = kLdsEdge + 1536 * 2;
-constexpr int kLdsVbase = kLdsCfg + 344;
-constexpr int kLdsTbase = kLdsVbase + 344 * 2;
-constexpr int kLdsIns = ((kLdsTbase + 344 * 2) + 7) & ~7;
-constexpr int kLdsQ = kLdsIns + 8 * 8;
-constexpr int kLdsMpu = ((kLdsQ + 8) + 15) & ~15;
-constexpr int kLdsTables = (int)((sizeof(CubeTablesDev) + 15) & ~(size_t)15);
+struct MpuLds {
+    uint16_t edgeVid[1536];             // passes 2-3: the vertex id on each lattice edge (CellEdge::slot)
+    uint8_t cfg[344];                   // per cell: its config,
+    uint16_t firstV[344], firstT[344];  // ... its first vertex id and first triangle id (pass 1)
+    alignas(8) uint64_t ins[8];         // the inside bits of the S2 cache
+    uint32_t q[2];                      // a spare word, qt (the tree split's triangle base)
+};
+constexpr int kLdsMpu = (int)((sizeof(MpuLds) + 15) & ~(size_t)15);
+static_assert(kLdsMpu == 4864 && __builtin_offsetof(MpuLds, ins) == 4792, "what the host sizes the launch by");
 constexpr int kLdsWaveSlots = kMpusPerBlock * kLdsMpu;  // interpreter slots follow
 
 // Last cell c in [0, 343) with first[c] <= r (first[] = exclusive prefix of per-cell
@@ -1098,6 +1129,267 @@ __device__ __forceinline__ void mpu_sync() {
     }
 }
 
+// k_front: one lane waits for entry e of sub-queue q (QueueEntry's protocol) and returns its
+// slot | live << 31.  Live once the ready word carries the run's tag; an entry that is still
+// untagged once every S1 block of q has published (s1Done; each block counts itself after its
+// waves' entries and tags left them) is past the sub-queue's end.  The wait is bounded (test
+// hook PSGPU_OPT_DEBUG bit 27: a few spins against S1 blocks held back ~40 us): a broken
+// protocol is flagged (error bit 4), finish re-runs as separate launches.
+__device__ __forceinline__ uint32_t acquire_front(const Params& p, uint32_t q, uint32_t e) {
+    const uint32_t slotq = q * p.fqCap + e, live = 0x80000000u;
+    if (e >= p.fqCap) return slotq;
+    const uint32_t tag = front_tag(p);
+    const uint32_t need = p.preBlocks > q ? (p.preBlocks - q + 7u) / 8u : 0u;  // S1 blocks of q
+    for (uint32_t spins = 0;; ++spins) {
+        if (QueueEntry::get<true>(&p.fqReady[slotq]) == tag) return slotq | live;
+        if ((spins & 7u) == 7u && QueueEntry::get<true>(&p.ctr->shard[q].s1Done) >= need)
+            return slotq | (QueueEntry::get<true>(&p.fqReady[slotq]) == tag ? live : 0u);
+        if (spins > ((p.debug & (1u << 27)) ? 8u : (1u << 22))) {
+            atomicOr(&p.ctr->error, 4u);
+            return slotq;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+}
+
+// k_mpu: the slot of the d-th queued survivor in shard order (dense over the 64 shard queues;
+// sIncl: the inclusive scan of the shard counts, lane s reads shard s's), d below the total
+__device__ __forceinline__ uint32_t acquire_queued(const Params& p, const uint32_t* sIncl, uint32_t d,
+                                                   uint32_t incl) {
+    const uint32_t pshard = (uint32_t)__popcll(ballot(incl <= d));  // first shard whose prefix passes d
+    const uint32_t pidx = d - (pshard ? sIncl[pshard - 1] : 0u);
+    return uniform(pshard * p.pShardCap + pidx);
+}
+
+// The tree split's S2 exchange: per wave of the block its part's values of the 8 x-slices
+__device__ __forceinline__ auto s2_parts() -> float (*)[8][64] {
+    __shared__ float s[4][8][64];
+    return s;
+}
+
+// S2 (:550-610), block-level: every wave of the block calls it, with or without an MPU (live),
+// and meets the one barrier in it (mpu_sync: the block's when the tree split gives an MPU two
+// waves), between phase stamps 3 and 4.  Before it the wave's walk of the 8x8x8 corner cache of
+// the MPU at o: lane = y*8 + z, the 8 x-slices per lane; quads = 4 consecutive z.  The field
+// values never leave registers: pass 1 needs only their inside bits, ins[x] bit y*8 + z (lane
+// order), which go through the MPU's sIns; with the tree split the wave walks subtree `wave %
+// SPLIT` of the root, the two parts' values go through LDS and both waves combine and ballot
+// them.  Returns the count of inside corners; ins[] is zero without an MPU.
+template <class EV, int SPLIT>
+__device__ __forceinline__ uint32_t block_s2_inside_bits(EV& ev, const Params& p, bool live, const float o[3],
+                                                         const CullMask& cm, int wave, uint64_t* sIns,
+                                                         uint64_t ins[8]) {
+    constexpr int NX = 8;  // x-slices of the S2 cache, all walked by this wave
+    const int lane = lane_id();
+    float fs[NX];
+    if (live) {
+        const float cs = p.cs;
+        const int y = lane >> 3, z = lane & 7;
+        const float py = o[1] + (float)y * cs;
+        const float pz = o[2] + (float)z * cs;
+        phase_stamp(p, 2);
+        float pxs[NX], pys[NX], pzs[NX];
+#pragma unroll
+        for (int x = 0; x < NX; ++x) {
+            pxs[x] = o[0] + (float)x * cs;
+            pys[x] = py;
+            pzs[x] = pz;
+        }
+        if constexpr (SPLIT > 1) {
+            if (wave % SPLIT == 0) ev.template evaln_part<4, false, 8, 0>(pxs, pys, pzs, cm, fs, nullptr);
+            else ev.template evaln_part<4, false, 8, 1>(pxs, pys, pzs, cm, fs, nullptr);
+#pragma unroll
+            for (int x = 0; x < NX; ++x) s2_parts()[wave][x][lane] = fs[x];
+        } else {
+#if PSGPU_S2_N == 1
+            // one walk per x-slice in a runtime loop: the walk's code stays resident in the
+            // instruction cache (unrolled copies of a 32-primitive walk do not fit)
+#pragma unroll 1
+            for (int h = 0; h < NX; ++h) fs[h] = ev.template eval<4, false>(pxs[h], py, pz, cm, nullptr);
+#else
+#pragma unroll
+            for (int h = 0; h < NX; h += PSGPU_S2_N)
+                ev.template evaln<4, false, PSGPU_S2_N>(pxs + h, pys + h, pzs + h, cm, fs + h, nullptr);
+#endif
+#pragma unroll
+            for (int x = 0; x < NX; ++x) {
+                const uint64_t b = ballot(fs[x] >= 0.5f);
+                if (lane == 0) sIns[x] = b;
+            }
+        }
+    }
+    phase_stamp(p, 3);
+    mpu_sync<SPLIT>();
+    phase_stamp(p, 4);
+    uint32_t inside = 0;
+#pragma unroll
+    for (int x = 0; x < NX; ++x) ins[x] = SPLIT == 1 && live ? sIns[x] : 0ull;
+    if constexpr (SPLIT > 1) {
+        if (live) {
+            const int first = wave / SPLIT * SPLIT;  // the MPU's first wave
+            float rv[NX], lv[NX];
+#pragma unroll
+            for (int x = 0; x < NX; ++x) {
+                rv[x] = s2_parts()[first][x][lane];
+                lv[x] = s2_parts()[first + 1][x][lane];
+            }
+            ev.template combine<false, 8>(rv, nullptr, lv, nullptr, cm, fs, nullptr);
+#pragma unroll
+            for (int x = 0; x < NX; ++x) ins[x] = ballot(fs[x] >= 0.5f);
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < NX; ++x) inside += __popcll(ins[x]);
+    return inside;
+}
+
+// S3 pass 1 (:647-691): config per cell (bit c = x*4 + y*2 + z, inside = f >= 0.5),
+// owned sign-changing edges (new vertices) and triangles; wave prefix sums give
+// the reference's discovery order over cells (i,j,k): one x-slab i per step, lane
+// j*8 + k, so the cell's corners are bits lane + {0, 1, 8, 9} of ins[i] and ins[i+1].
+// Every wave of the MPU computes the counts; the first writes the tables (per cell its
+// config and its first vertex and triangle ids).  Returns V | T << 16 (both <= 343 * 12
+// per MPU: no carry between the halves).
+__device__ __forceinline__ uint32_t count_cells(const CubeTablesDev* tab, const uint64_t ins[8], bool first,
+                                                MpuLds& L) {
+    const int lane = lane_id();
+    uint32_t carry = 0;
+    const int j = lane >> 3, k = lane & 7;
+    const bool cellLane = j < 7 && k < 7;
+    const uint32_t ownJK = tab->own[(j == 0 ? 2 : 0) | (k == 0 ? 1 : 0)];    // cells with i > 0
+    const uint32_t ownJK0 = tab->own[4 | (j == 0 ? 2 : 0) | (k == 0 ? 1 : 0)];  // the i == 0 slab
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const int c = i * 49 + j * 7 + k;
+        const uint32_t b0 = (uint32_t)(ins[i] >> lane), b1 = (uint32_t)(ins[i + 1] >> lane);
+        uint32_t cfg = 0;
+        if (cellLane) cfg = (b0 & 3u) | ((b0 >> 6) & 12u) | ((b1 & 3u) << 4) | (((b1 >> 8) & 3u) << 6);
+        uint32_t nvt = 0;
+        if (cfg != 0 && cfg != 255) {
+            const uint32_t cn = tab->crossNtri[cfg];
+            nvt = (uint32_t)__popc((i == 0 ? ownJK0 : ownJK) & cn & 0xfffu) | (cn & 0xffff0000u);
+        }
+        const uint32_t svt = wave_incl_scan(nvt);  // one scan for both counts
+        if (cellLane && first) {
+            const uint32_t id = carry + svt - nvt;
+            L.cfg[c] = (uint8_t)cfg;
+            L.firstV[c] = (uint16_t)(id & 0xffffu);
+            L.firstT[c] = (uint16_t)(id >> 16);
+        }
+        carry += lane_value(svt, 63);
+    }
+    return carry;
+}
+
+// Block reservation (block-level: the three steps of one rendezvous over these shared words).
+// The block reserves its vertex records with one atomic into shard blk & 63, its MPUs back to
+// back (the 64-record batches of k_vertex / k_finish then straddle MPUs of one S1 brick, whose
+// live primitive sets overlap: DESIGN.md §4).  reset: before the prologue's barrier, which every
+// wave of the block reaches.  arrive: one lane per MPU, after S3 pass 1, leaves its V (0 without
+// surface) in slot order and counts itself in; the last to arrive has all of them and reserves
+// their sum.  Its wait for the atomic is the block's: the base is published at the barrier that
+// follows (making each wave's first batch of records before the barrier, to hide that wait,
+// measured the same: profiles/r07_block_reserve_ab.txt).  base_of: after that barrier, the
+// block's base + the V of the earlier slots.
+template <int MPB>
+struct BlockReserve {
+    uint32_t v[MPB], arrived, base;
+    __device__ __forceinline__ void reset() { arrived = 0u; }  // by one thread
+    __device__ __forceinline__ void arrive(const Params& p, uint32_t blk, int slot, uint32_t V) {
+        v[slot] = V;
+        if (__hip_atomic_fetch_add(&arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == MPB - 1u) {
+            uint32_t sum = 0;
+#pragma unroll
+            for (int k = 0; k < MPB; ++k) sum += v[k];
+            base = sum ? atomicAdd(&p.ctr->shard[blk & (kShards - 1)].v, sum) : 0u;
+        }
+    }
+    __device__ __forceinline__ uint32_t base_of(int slot) const {
+        uint32_t qv = base;
+#pragma unroll
+        for (int k = 0; k < MPB - 1; ++k)
+            if (k < slot) qv += v[k];
+        return qv;
+    }
+};
+
+// The decodes passes 2 and 3 share (if they disagreed, pass 3 would read an edgeVid slot that
+// pass 2 did not write): cell c -> (i, j, k), and edge ed of that cell -> the lattice edge it
+// is (CellEdge): low corner (sx, sy, sz) of the 8x8x8 cache and axis, from the table's edgeBits.
+struct CellIjk {
+    int i, j, k;
+};
+__device__ __forceinline__ CellIjk cell_ijk(int c) { return CellIjk{c / 49, (c / 7) % 7, c % 7}; }
+struct CellEdge {
+    int sx, sy, sz, ax;
+    __device__ __forceinline__ CellEdge(uint64_t edgeBits, const CellIjk& c, int ed) {
+        const int eb = (int)((edgeBits >> (5 * ed)) & 31u), c1 = eb & 7;
+        sx = c.i + ((c1 >> 2) & 1), sy = c.j + ((c1 >> 1) & 1), sz = c.k + (c1 & 1), ax = eb >> 3;
+    }
+    __device__ __forceinline__ int slot() const { return ((sx * 8 + sy) * 8 + sz) * 3 + ax; }  // in edgeVid
+};
+
+// pass 2 (:703-762), one lane per new vertex r (batches of 64 dealt to the MPU's waves
+// in turn): its cell is the last cell whose first vertex id is <= r; it is that cell's
+// k-th owned crossing edge in first-occurrence order of the row, k = r - first id.
+// Records are written coalesced, from qv (BlockReserve::base_of) on.
+template <int WPM>
+__device__ __forceinline__ void vertex_records(const Params& p, uint64_t edgeBits, MpuLds& L, VertexKey* vk,
+                                               uint32_t w, uint32_t V, uint32_t qv, int part) {
+    const CubeTablesDev* tab = p.tables;
+    const int lane = lane_id();
+    for (uint32_t b0 = (uint32_t)part * 64u; b0 < V; b0 += 64u * WPM) {
+        const uint32_t r = b0 + (uint32_t)lane;
+        if (r < V) {
+            const int c = find_cell(L.firstV, r);
+            const uint32_t cfg = L.cfg[c];
+            const CellIjk at = cell_ijk(c);
+            const uint32_t own = tab->own[(at.i == 0 ? 4 : 0) | (at.j == 0 ? 2 : 0) | (at.k == 0 ? 1 : 0)];
+            const uint64_t order = tab->order[cfg];
+            uint32_t left = r - L.firstV[c];
+            int ed = 0;
+            for (int q = 0; q < 12; ++q) {  // the (left+1)-th owned edge of the row order
+                ed = (int)((order >> (4 * q)) & 15u);
+                if ((own >> ed) & 1u) {
+                    if (left == 0u) break;
+                    --left;
+                }
+            }
+            const CellEdge e(edgeBits, at, ed);
+            L.edgeVid[e.slot()] = (uint16_t)r;
+            const uint32_t key = (uint32_t)e.sx | ((uint32_t)e.sy << 3) | ((uint32_t)e.sz << 6) | ((uint32_t)e.ax << 9);
+            const uint32_t g = qv + r;
+            if (g < p.vShardCap) vk[g] = VertexKey{w, r | (key << 16)};
+        }
+    }
+}
+
+// pass 3 (S6, :816-825), one lane per triangle r: its cell (last first-id <= r) and
+// the (r - first)-th triangle of the cell's table row; records from qt on
+template <int WPM>
+__device__ __forceinline__ void triangle_records(const Params& p, uint64_t edgeBits, const MpuLds& L, TriRec* tq,
+                                                 uint32_t w, uint32_t T, uint32_t qt, int part) {
+    const int lane = lane_id();
+    for (uint32_t b0 = (uint32_t)part * 64u; b0 < T; b0 += 64u * WPM) {
+        const uint32_t r = b0 + (uint32_t)lane;
+        if (r < T) {
+            const int c = find_cell(L.firstT, r);
+            const uint32_t t = r - L.firstT[c];
+            const CellIjk at = cell_ijk(c);
+            const uint64_t row = p.tables->row[L.cfg[c]];
+            uint32_t v[3];
+#pragma unroll
+            for (int sv = 0; sv < 3; ++sv) {
+                const int ed = (int)((row >> (4 * (t * 3 + sv))) & 15u);
+                v[sv] = L.edgeVid[CellEdge(edgeBits, at, ed).slot()];
+            }
+            const uint32_t g = qt + r;
+            if (g < p.tShardCap)
+                tq[g] = TriRec{r | ((v[2] >> 10) << 11) | ((w >> 6) << 12), v[0] | (v[1] << 11) | ((v[2] & 1023u) << 22)};
+        }
+    }
+}
+
 // Per-MPU body: one wavefront per MPU that passed S1 (and was not proven empty), 4
 // wavefronts per block.  Every wave of a block reaches every barrier: waves without an MPU
 // (past the last survivor) or whose MPU has no surface just skip the work.
@@ -1119,52 +1411,19 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     const int lane = lane_id();
     const int slot = wave / WPM;  // the block's MPU this wave works on
     const int part = wave % WPM;  // its subtree of the root (SPLIT 2), and its turn in the record passes
-    constexpr int NX = 8;         // x-slices of the S2 cache, all walked by this wave
     phase_stamp(p, 0);
     uint32_t d = blk * (uint32_t)MPB + (uint32_t)slot;
     ModelPtr M = as_const(p.model);
     const CubeTablesDev* tab = p.tables;  // global: L1 / L2 resident (an LDS copy per block measured slower, r05)
     bool live;
     uint32_t slotq = 0;
-    // The block reserves its vertex records with one atomic into shard blk & 63, its MPUs back
-    // to back (the 64-record batches of k_vertex / k_finish then straddle MPUs of one S1 brick,
-    // whose live primitive sets overlap: DESIGN.md §4): the MPUs exchange their V (0 without
-    // surface) and arrive here after S3 pass 1, and the last one reserves (zeroed before the
-    // prologue's barrier, which every wave of the block reaches)
-    __shared__ uint32_t sResV[MPB], sResArrive, sResBase;
-    if (threadIdx.x == 0) sResArrive = 0u;
+    __shared__ BlockReserve<MPB> sRes;
+    if (threadIdx.x == 0) sRes.reset();
     if constexpr (FRONT) {
         const uint32_t q = blk & 7u, e = (blk >> 3) * (uint32_t)MPB + (uint32_t)slot;
         d = (e << 3) | q;  // spreads the MPU's vertex records over the shards
         __shared__ uint32_t sFront[4];  // per MPU of the block: entry | live << 31
-        if (part == 0 && lane == 0) {
-            slotq = q * p.fqCap + e;
-            bool lv = false;
-            if (e < p.fqCap) {
-                const uint32_t tag = front_tag(p);
-                const uint32_t need = p.preBlocks > q ? (p.preBlocks - q + 7u) / 8u : 0u;  // S1 blocks of q
-                for (uint32_t spins = 0;; ++spins) {
-                    if (__hip_atomic_load(&p.fqReady[slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag) {
-                        lv = true;
-                        break;
-                    }
-                    // every S1 block of q published (each after its waves' entries and tags left them)
-                    if ((spins & 7u) == 7u &&
-                        __hip_atomic_load(&p.ctr->shard[q].s1Done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need) {
-                        lv = __hip_atomic_load(&p.fqReady[slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag;
-                        break;
-                    }
-                    // bounded (test hook PSGPU_OPT_DEBUG bit 27: a few spins against S1 blocks held
-                    // back ~40 us): a broken protocol is flagged, finish re-runs as separate launches
-                    if (spins > ((p.debug & (1u << 27)) ? 8u : (1u << 22))) {
-                        atomicOr(&p.ctr->error, 4u);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            sFront[slot] = slotq | (lv ? 0x80000000u : 0u);
-        }
+        if (part == 0 && lane == 0) sFront[slot] = acquire_front(p, q, e);
         __syncthreads();  // the MPU's other wave reads the entry after the barrier its poller joined
         bool any = false;
 #pragma unroll
@@ -1181,141 +1440,31 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
             sIncl[lane] = wave_incl_scan(cnt);
         }
         __syncthreads();
-        // MPU d = block * MPB + slot is the d-th queued survivor in shard order (dense over
-        // the 64 shard queues: lane s holds shard s's count); the grid is sized by the host
-        // from the last finished run, and a run with more survivors than that is re-run by finish()
+        // the grid is sized by the host from the last finished run, and a run with more
+        // survivors than that is re-run by finish()
         const uint32_t incl = sIncl[lane];
         const uint32_t pcount = sIncl[kShards - 1];
         if (blk * (uint32_t)MPB >= pcount) return;  // whole block past the last survivor
         live = d < pcount;
-        if (live) {
-            const uint32_t pshard = (uint32_t)__popcll(ballot(incl <= d));  // first shard whose prefix passes d
-            const uint32_t pidx = d - (pshard ? sIncl[pshard - 1] : 0u);
-            slotq = uniform(pshard * p.pShardCap + pidx);
-        }
+        if (live) slotq = acquire_queued(p, sIncl, d, incl);
     }
-    uint32_t m = 0, w = 0;
+    QueueEntry e{0u, CullMask{0ull, 0ull}};
+    uint32_t w = 0;
     float o[3] = {0.0f, 0.0f, 0.0f};
-    CullMask cm{0ull, 0ull};
     if (live) {
-        if (FRONT) {  // published in this launch: sc1 loads (the stores were sc1)
-            m = uniform(__hip_atomic_load(&p.pq[slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (p.cull) {
-                cm.lo = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                cm.hi = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                cm.inLo = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (M->ctOps > 64u)  // the second word only for trees that have such ops
-                    cm.inHi = uniform64(__hip_atomic_load(&p.pqMask[4 * slotq + 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            }
-        } else {
-            m = uniform(p.pq[slotq]);
-            if (p.cull) {  // the MPU box's culling and op-inside masks, made by k_precheck: in
-                           // SGPRs, so every per-primitive culling test and every skip of an
-                           // op-box pruning test of the walk is a scalar branch
-                cm.lo = uniform64(p.pqMask[4 * slotq]);
-                cm.hi = uniform64(p.pqMask[4 * slotq + 1]);
-                cm.inLo = uniform64(p.pqMask[4 * slotq + 2]);
-                cm.inHi = uniform64(p.pqMask[4 * slotq + 3]);
-            }
-        }
-        *item = m;
-        w = m - p.mpuBegin;  // slot of the MPU in the range: counts / offsets index
-        mpu_origin(p, m, o);
+        e = QueueEntry::load<FRONT>(p, M, slotq);
+        *item = e.m;
+        w = e.m - p.mpuBegin;  // slot of the MPU in the range: counts / offsets index
+        mpu_origin(p, e.m, o);
     }
     phase_stamp(p, 1);
-    unsigned char* base = smem + slot * kLdsMpu;
-    uint16_t* edgeVid = reinterpret_cast<uint16_t*>(base + kLdsEdge);
-    uint8_t* cellCfg = base + kLdsCfg;
-    uint16_t* cellV = reinterpret_cast<uint16_t*>(base + kLdsVbase);
-    uint16_t* cellT = reinterpret_cast<uint16_t*>(base + kLdsTbase);
-    uint64_t* sIns = reinterpret_cast<uint64_t*>(base + kLdsIns);
-    uint32_t* sQ = reinterpret_cast<uint32_t*>(base + kLdsQ);
+    MpuLds& L = *reinterpret_cast<MpuLds*>(smem + slot * kLdsMpu);
     EV ev(M, reinterpret_cast<float*>(smem + kLdsWaveSlots + wave * p.slotsPerLane * 64 * 4) + lane);
-    const float cs = p.cs;
-
-    float fs[NX];
-    if (live) {
-        // S2 (:550-610): corner (x, y, z) of the 8x8x8 cache, lane = y*8 + z, the 8 x-slices
-        // per lane; quads = 4 consecutive z
-        const int y = lane >> 3, z = lane & 7;
-        const float py = o[1] + (float)y * cs;
-        const float pz = o[2] + (float)z * cs;
-        phase_stamp(p, 2);
-        float pxs[NX], pys[NX], pzs[NX];
-#pragma unroll
-        for (int x = 0; x < NX; ++x) {
-            pxs[x] = o[0] + (float)x * cs;
-            pys[x] = py;
-            pzs[x] = pz;
-        }
-        if constexpr (SPLIT > 1) {
-            if (part == 0) ev.template evaln_part<4, false, 8, 0>(pxs, pys, pzs, cm, fs, nullptr);
-            else ev.template evaln_part<4, false, 8, 1>(pxs, pys, pzs, cm, fs, nullptr);
-        } else {
-#if PSGPU_S2_N == 1
-            // one walk per x-slice in a runtime loop: the walk's code stays resident in the
-            // instruction cache (unrolled copies of a 32-primitive walk do not fit)
-#pragma unroll 1
-            for (int h = 0; h < NX; ++h) fs[h] = ev.template eval<4, false>(pxs[h], py, pz, cm, nullptr);
-#else
-#pragma unroll
-            for (int h = 0; h < NX; h += PSGPU_S2_N)
-                ev.template evaln<4, false, PSGPU_S2_N>(pxs + h, pys + h, pzs + h, cm, fs + h, nullptr);
-#endif
-            // inside bits of the 8x8x8 corners: ins[x] bit y*8 + z (lane order)
-#pragma unroll
-            for (int x = 0; x < NX; ++x) {
-                const uint64_t b = ballot(fs[x] >= 0.5f);
-                if (lane == 0) sIns[x] = b;
-            }
-        }
-    }
-    uint64_t ins[8];
-    uint32_t inside = 0;
-    if constexpr (SPLIT > 1) {  // the parts' values through LDS; both waves combine all 8 slices
-        __shared__ float sS2[4][8][64];
-        if (live) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) sS2[wave][x][lane] = fs[x];
-        }
-        phase_stamp(p, 3);
-        __syncthreads();
-        phase_stamp(p, 4);
-        if (live) {
-            float rv[8], lv[8], f8[8];
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-                rv[x] = sS2[slot * 2][x][lane];
-                lv[x] = sS2[slot * 2 + 1][x][lane];
-            }
-            ev.template combine<false, 8>(rv, nullptr, lv, nullptr, cm, f8, nullptr);
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-                ins[x] = ballot(f8[x] >= 0.5f);
-                inside += __popcll(ins[x]);
-            }
-        } else {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) ins[x] = 0ull;
-        }
-    } else {
-        phase_stamp(p, 3);
-        mpu_sync<WPM>();
-        phase_stamp(p, 4);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) {
-            ins[x] = live ? sIns[x] : 0ull;
-            inside += __popcll(ins[x]);
-        }
-    }
+    uint64_t ins[8];  // (block-level: the S2 barrier is in it)
+    const uint32_t inside = block_s2_inside_bits<EV, SPLIT>(ev, p, live, o, e.cm, wave, L.ins, ins);
     const bool work = live && inside != 0 && inside != 512 && !(p.debug & 1u);
     if (live && !work && part == 0 && lane == 0) p.counts[w] = 0ull;  // no vertices, no triangles
 
-    // S3 pass 1 (:647-691): config per cell (bit c = x*4 + y*2 + z, inside = f >= 0.5),
-    // owned sign-changing edges (new vertices) and triangles; wave prefix sums give
-    // the reference's discovery order over cells (i,j,k): one x-slab i per step, lane
-    // j*8 + k, so the cell's corners are bits lane + {0, 1, 8, 9} of ins[i] and ins[i+1].
-    // Every wave of the MPU computes V and T; the first writes the tables and counters.
     const uint64_t edgeBits = tab->edge;
     uint32_t V = 0, T = 0;
     // WPM 1: the triangle queue's base stays in lane 0's registers (the returning atomic is not
@@ -1323,141 +1472,37 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     // record passes hold half of k_mpu's parked cycles)
     uint32_t qtAtomic = 0u;
     if (work) {
-        uint32_t carry = 0;  // V | T << 16 (both <= 343 * 12 per MPU: no carry between the halves)
-        const int j = lane >> 3, k = lane & 7;
-        const bool cellLane = j < 7 && k < 7;
-        const uint32_t ownJK = tab->own[(j == 0 ? 2 : 0) | (k == 0 ? 1 : 0)];    // cells with i > 0
-        const uint32_t ownJK0 = tab->own[4 | (j == 0 ? 2 : 0) | (k == 0 ? 1 : 0)];  // the i == 0 slab
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const int c = i * 49 + j * 7 + k;
-            const uint32_t b0 = (uint32_t)(ins[i] >> lane), b1 = (uint32_t)(ins[i + 1] >> lane);
-            uint32_t cfg = 0;
-            if (cellLane)
-                cfg = (b0 & 3u) | ((b0 >> 6) & 12u) | ((b1 & 3u) << 4) | (((b1 >> 8) & 3u) << 6);
-            uint32_t nvt = 0;
-            if (cfg != 0 && cfg != 255)
-            {
-                const uint32_t cn = tab->crossNtri[cfg];
-                nvt = (uint32_t)__popc((i == 0 ? ownJK0 : ownJK) & cn & 0xfffu) | (cn & 0xffff0000u);
-            }
-            const uint32_t svt = wave_incl_scan(nvt);  // one scan for both counts
-            if (cellLane && part == 0) {
-                const uint32_t first = carry + svt - nvt;
-                cellCfg[c] = (uint8_t)cfg;
-                cellV[c] = (uint16_t)(first & 0xffffu);
-                cellT[c] = (uint16_t)(first >> 16);
-            }
-            carry += lane_value(svt, 63);
-        }
-        V = carry & 0xffffu;
-        T = carry >> 16;
+        const uint32_t vt = count_cells(tab, ins, part == 0, L);
+        V = vt & 0xffffu;
+        T = vt >> 16;
         if (part == 0) {
             const uint32_t shard = d & (kShards - 1);
             if (lane == 0) {
                 qtAtomic = atomicAdd(&p.ctr->shard[w & (kShards - 1)].t, T);  // TriRec: shard = w & 63
-                if (WPM > 1) sQ[1] = qtAtomic;
+                if (WPM > 1) L.q[1] = qtAtomic;
                 p.counts[w] = (uint64_t)V | ((uint64_t)T << 32);
                 if (T > 0) atomicAdd(&p.ctr->shard[shard].s, 1u);
-                if (V > 512u || T > 512u) atomicMin(&p.ctr->firstOverflow, (int)m);
+                if (V > 512u || T > 512u) atomicMin(&p.ctr->firstOverflow, (int)e.m);
             }
         }
     }
     phase_stamp(p, 5);
 #if PSGPU_MPU_LIVE_STAMP
-    // phase word 7 (measurement builds only): the wave's live primitives, its MPU's V and T
-    if ((p.debug & 4096u) && p.stamps && lane == 0 && live) {
-        const uint32_t sw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (sw < p.stampCap)
-            p.stamps[3 * (size_t)kNumStampKernels * p.stampCap + 8 * (size_t)sw + 7] =
-                (uint64_t)(128 - __popcll(cm.lo) - __popcll(cm.hi)) | ((uint64_t)V << 16) | ((uint64_t)T << 32);
-    }
+    // measurement builds only: the MPU's V and T beside the wave's live primitives
+    if (live) stamp_live_word(p, p.debug & 4096u, e.cm, ((uint64_t)V << 16) | ((uint64_t)T << 32));
 #endif
     const bool recs = work && !(p.debug & 2u);  // ablation bit 1: pass 1 only
-    // the block's rendezvous: every MPU leaves its V in slot order and counts itself in; the
-    // last to arrive has all of them and reserves their sum in shard blk & 63.  Its wait for
-    // the atomic is the block's: the base is published at the barrier (making each wave's
-    // first batch of records before the barrier, to hide that wait, measured the same:
-    // profiles/r07_block_reserve_ab.txt)
-    if (part == 0 && lane == 0) {
-        sResV[slot] = V;
-        if (__hip_atomic_fetch_add(&sResArrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) ==
-            (uint32_t)MPB - 1u) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int k = 0; k < MPB; ++k) sum += sResV[k];
-            sResBase = sum ? atomicAdd(&p.ctr->shard[blk & (kShards - 1)].v, sum) : 0u;
-        }
-    }
+    if (part == 0 && lane == 0) sRes.arrive(p, blk, slot, V);
     __syncthreads();
     if (WPM == 1 && !work) return;
     VertexKey* vk = p.vk + (size_t)(blk & (kShards - 1)) * p.vShardCap;
     TriRec* tq = p.tq + (size_t)(w & (kShards - 1)) * p.tShardCap;
-
-    // pass 2 (:703-762), one lane per new vertex r (batches of 64 dealt to the MPU's waves
-    // in turn): its cell is the last cell whose first vertex id is <= r; it is that cell's
-    // k-th owned crossing edge in first-occurrence order of the row, k = r - first id.
-    // Records are written coalesced.
-    if (recs) {
-        uint32_t qv = sResBase;  // the block's base + the V of its earlier slots
-#pragma unroll
-        for (int k = 0; k < MPB - 1; ++k)
-            if (k < slot) qv += sResV[k];
-        for (uint32_t b0 = (uint32_t)part * 64u; b0 < V; b0 += 64u * WPM) {
-            const uint32_t r = b0 + (uint32_t)lane;
-            if (r < V) {
-                const int c = find_cell(cellV, r);
-                const uint32_t cfg = cellCfg[c];
-                const int i = c / 49, j = (c / 7) % 7, k = c % 7;
-                const uint32_t own = tab->own[(i == 0 ? 4 : 0) | (j == 0 ? 2 : 0) | (k == 0 ? 1 : 0)];
-                const uint64_t order = tab->order[cfg];
-                uint32_t left = r - cellV[c];
-                int ed = 0;
-                for (int q = 0; q < 12; ++q) {  // the (left+1)-th owned edge of the row order
-                    ed = (int)((order >> (4 * q)) & 15u);
-                    if ((own >> ed) & 1u) {
-                        if (left == 0u) break;
-                        --left;
-                    }
-                }
-                const int eb = (int)((edgeBits >> (5 * ed)) & 31u);
-                const int c1 = eb & 7, ax = eb >> 3;
-                const int sx = i + ((c1 >> 2) & 1), sy = j + ((c1 >> 1) & 1), sz = k + (c1 & 1);
-                edgeVid[((sx * 8 + sy) * 8 + sz) * 3 + ax] = (uint16_t)r;
-                const uint32_t key = (uint32_t)sx | ((uint32_t)sy << 3) | ((uint32_t)sz << 6) | ((uint32_t)ax << 9);
-                const uint32_t g = qv + r;
-                if (g < p.vShardCap) vk[g] = VertexKey{w, r | (key << 16)};
-            }
-        }
-    }
+    if (recs) vertex_records<WPM>(p, edgeBits, L, vk, w, V, sRes.base_of(slot), part);
     phase_stamp(p, 6);
     mpu_sync<WPM>();
     if (!recs || (p.debug & 4u)) return;  // ablation bit 2: no triangles
-
-    // pass 3 (S6, :816-825), one lane per triangle r: its cell (last first-id <= r) and
-    // the (r - first)-th triangle of the cell's table row
-    const uint32_t qt = WPM > 1 ? sQ[1] : lane_value(qtAtomic, 0);
-    for (uint32_t b0 = (uint32_t)part * 64u; b0 < T; b0 += 64u * WPM) {
-        const uint32_t r = b0 + (uint32_t)lane;
-        if (r < T) {
-            const int c = find_cell(cellT, r);
-            const uint32_t t = r - cellT[c];
-            const int i = c / 49, j = (c / 7) % 7, k = c % 7;
-            const uint64_t row = tab->row[cellCfg[c]];
-            uint32_t v[3];
-#pragma unroll
-            for (int sv = 0; sv < 3; ++sv) {
-                const int ed = (int)((row >> (4 * (t * 3 + sv))) & 15u);
-                const int eb = (int)((edgeBits >> (5 * ed)) & 31u);
-                const int c1 = eb & 7, ax = eb >> 3;
-                const int sx = i + ((c1 >> 2) & 1), sy = j + ((c1 >> 1) & 1), sz = k + (c1 & 1);
-                v[sv] = edgeVid[((sx * 8 + sy) * 8 + sz) * 3 + ax];
-            }
-            const uint32_t g = qt + r;
-            if (g < p.tShardCap)
-                tq[g] = TriRec{r | ((v[2] >> 10) << 11) | ((w >> 6) << 12), v[0] | (v[1] << 11) | ((v[2] & 1023u) << 22)};
-        }
-    }
+    const uint32_t qt = WPM > 1 ? L.q[1] : lane_value(qtAtomic, 0);
+    triangle_records<WPM>(p, edgeBits, L, tq, w, T, qt, part);
 }
 
 // Batches of `per` records over the kShards queues: lane l holds shard l's batch

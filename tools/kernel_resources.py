@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-K_LDS_MPU = 4864            # psgpu_device.h kLdsMpu (6400 with PSGPU_MPU_MAPS 1)
+K_LDS_MPU = 4864            # psgpu_device.h kLdsMpu
 MPU_DYNAMIC_LDS = 4 * K_LDS_MPU  # mpu_lds_bytes(0), kMpusPerBlock = 4
 MPU_S_DYNAMIC_LDS = 2 * K_LDS_MPU  # the tree-split k_mpu: 2 MPUs per block
 ROLE = {"jit_precheck": "k_precheck", "jit_mpu": "k_mpu", "jit_vertex": "k_vertex (quad, 16/wave)",
