@@ -284,6 +284,80 @@ int  psgpu_download_weld(psgpu_ctx* ctx, float* pos, float* nrm, float* col, uin
  * weld, then its five launches; returns the count filled. */
 int  psgpu_weld_times(psgpu_ctx* ctx, float* ms, int maxPhases, const char** names);
 
+/* ---- shells of the welded mesh: topology, area and volume ---------------------------------
+ * A shell is a connected component of the welded mesh: two welded vertices are connected when
+ * a triangle uses both; a welded vertex in no triangle is a shell of its own with 0 triangles.
+ * Shells are ordered by their smallest welded vertex id, firstVertex.
+ *
+ * Edges.  For every undirected edge {lo < hi} used by triangles (a triangle corner pair with
+ * equal ids is no edge), f counts its uses in winding order lo->hi and b those in order hi->lo:
+ *     open          f + b == 1
+ *     flipped       f + b == 2 and f != b
+ *     non-manifold  f + b >= 3
+ *     regular       anything else
+ * An edge belongs to the shell of its vertices.  A shell is closed when it has triangles and
+ * no open, flipped or non-manifold edge.
+ *
+ * Reproducible measures.  Everything returned is a function of the welded arrays alone, area
+ * and volume included: two calls give the same bytes, and meshio.shells (plain numpy) gives
+ * them too.  Sums are exact integers, by this rule (IEEE double, no contraction, evaluated
+ * left to right as written):
+ *   1. per triangle (a, b, c), positions converted to double:
+ *        u = b - a, v = c - a
+ *        n  = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx)
+ *        A2 = sqrt(nx nx + ny ny + nz nz)
+ *        V6 = ax (by cz - bz cy) + ay (bz cx - bx cz) + az (bx cy - by cx)
+ *   2. M = the largest |coordinate| over the welded vertices, k = the smallest integer with
+ *      M < 2^k (0 for M = 0), L = ceil(log2(max(T, 2))), eA = 58 - 2k - L, eV = 58 - 3k - L
+ *   3. a term x at scale e: y = ldexp(x, e), hi = floor(y) as int64,
+ *      lo = floor((y - hi) 2^30) as int64
+ *   4. hi and lo are added into two int64 accumulators per shell and term (integer atomics:
+ *      any order gives the same sum)
+ *   5. a shell's value is ldexp((double)sumHi, -e) + ldexp((double)sumLo, -e - 30), divided by
+ *      2 for the area (A2, eA) and by 6 for the volume (V6, eV)
+ *   6. the mesh totals are the integer sums of the shells' accumulators, converted once
+ *   7. |u|, |v| < 2^(k+1) per coordinate, so |n| < 2^(2k+3) per coordinate,
+ *      A2 < sqrt(3) 2^(2k+3) < 2^(2k+4) and |V6| < 3 2^(3k+1) < 2^(3k+3): |hi| < 2^(62-L) and
+ *      0 <= lo < 2^30, so T <= 2^L terms keep every accumulator below 2^62.
+ * Coordinates must be finite.  Bounding boxes are exact float minima and maxima, with -0
+ * ordered below +0; those of an empty mesh are 0.  The volume is signed: > 0 for outward
+ * winding, < 0 for a cavity, and meaningful when the shell is closed. */
+typedef struct PsShell {
+    uint32_t firstVertex, ctVertices, ctTriangles, ctEdges;
+    uint32_t ctOpenEdges, ctNonManifoldEdges, ctFlippedEdges;
+    int32_t  euler;                 /* V - E + T */
+    double   area, volume;
+    float    bboxLo[3], bboxHi[3];
+} PsShell;
+typedef struct PsShellsInfo {       /* the whole mesh: counts are the sums over the shells */
+    uint32_t ctShells, ctClosedShells;
+    uint32_t ctVertices, ctTriangles, ctEdges, ctOpenEdges, ctNonManifoldEdges, ctFlippedEdges;
+    int32_t  euler;
+    uint32_t reserved;
+    double   area, volume;
+    float    bboxLo[3], bboxHi[3];
+} PsShellsInfo;
+typedef struct PsShellsDevice {     /* valid until the next weld / shells call / destroy */
+    const PsShell*  shells;         /* ctShells */
+    const uint32_t* vertexShell;    /* welded ctVertices: shell index of each vertex */
+    const uint32_t* triShell;       /* ctTriangles */
+} PsShellsDevice;
+/* The shells of the context's weld, on the context's stream; blocking.  PSGPU_RET_PARAM_ERROR
+ * unless the current run has been welded (psgpu_weld_device's rule); a new psgpu_weld
+ * invalidates the shells.  An empty weld has 0 shells.  The weld's arrays and the run are left
+ * untouched.  The buffers come with the first call, grow on demand and go with psgpu_destroy:
+ * a context that never asks pays nothing.  PSGPU_RET_DEVICE_ERROR if a bounded loop of a
+ * kernel ran out (a triangle naming no vertex; never on a weld's own arrays). */
+int  psgpu_weld_shells(psgpu_ctx* ctx, PsShellsInfo* info);
+/* The shells in HBM / on the host (any pointer may be NULL): PSGPU_RET_PARAM_ERROR before a
+ * successful psgpu_weld_shells of the current weld, and for a capacity below ctShells. */
+int  psgpu_weld_shells_device(psgpu_ctx* ctx, PsShellsDevice* out);
+int  psgpu_download_weld_shells(psgpu_ctx* ctx, PsShell* shells, uint32_t capacity, uint32_t* vertexShell,
+                                uint32_t* triShell);
+/* hipEvent times (ms) of the last psgpu_weld_shells with PSGPU_OPT_KERNEL_TIMING set: the
+ * whole call (its two host reads included), then its ten steps; returns the count filled. */
+int  psgpu_weld_shells_times(psgpu_ctx* ctx, float* ms, int maxPhases, const char** names);
+
 /* Per-MPU stats for every MPU in the last processed range (ctMPUs entries). */
 int  psgpu_download_stats(psgpu_ctx* ctx, PsMpuStats* stats);
 /* Scatter the last result into the reference PolyMPUs layout (vMPUs[0..ctMPUs)). */
@@ -568,6 +642,14 @@ int  psgpu_group_download_weld(psgpu_group* g, float* pos, float* nrm, float* co
  * and their copies (as far as they outlast the gather), the mark, then resolve, scan, emit
  * and map; returns the count filled. */
 int  psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char** names);
+/* The shells of the group's weld (psgpu_weld_shells' contract, above), on the welding part's
+ * device: PSGPU_RET_PARAM_ERROR unless the group's current run has been welded; a new
+ * psgpu_group_weld invalidates them; the buffers go with psgpu_group_destroy. */
+int  psgpu_group_weld_shells(psgpu_group* g, PsShellsInfo* info);
+int  psgpu_group_weld_shells_device(psgpu_group* g, PsShellsDevice* out);
+int  psgpu_group_download_weld_shells(psgpu_group* g, PsShell* shells, uint32_t capacity, uint32_t* vertexShell,
+                                      uint32_t* triShell);
+int  psgpu_group_weld_shells_times(psgpu_group* g, float* ms, int maxPhases, const char** names);
 int  psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCtMPUs);
 /* Blocking drop-in for PS::SIMDPOLY::Polygonize over every device of the group. */
 int  psgpu_group_polygonize_mpus(psgpu_group* g, float cellsize, const PsSoaBlobPrims* prims,
@@ -621,6 +703,8 @@ static_assert(offsetof(PsMPU, ctVertices) == 21504, "ctVertices offset");
 static_assert(offsetof(PsMPU, bboxLo) == 21508, "MPU bboxLo offset");
 static_assert(offsetof(PsMPU, ctFieldEvals) == 21520, "ctFieldEvals offset");
 static_assert(sizeof(PsMpuProcessStats) == 32, "MPUSTATS size (LP64)");
+static_assert(sizeof(PsShell) == 72, "PsShell size");
+static_assert(sizeof(PsShellsInfo) == 80, "PsShellsInfo size");
 static_assert(offsetof(PsMpuProcessStats, threadID) == 8, "MPUSTATS threadID offset");
 static_assert(offsetof(PsMpuProcessStats, tickStart) == 16, "MPUSTATS tickStart offset");
 static_assert(offsetof(PsMpuProcessStats, tickEnd) == 24, "MPUSTATS tickEnd offset");
@@ -630,6 +714,8 @@ _Static_assert(sizeof(PsSoaBlobOps) == 5636, "SOABlobOps size");
 _Static_assert(sizeof(PsSoaPrimMatrices) == 6148, "SOABlobPrimMatrices size");
 _Static_assert(sizeof(PsSoaBoxMatrices) == 8196, "SOABlobBoxMatrices size");
 _Static_assert(sizeof(PsMPU) == 21524, "MPU size");
+_Static_assert(sizeof(PsShell) == 72, "PsShell size");
+_Static_assert(sizeof(PsShellsInfo) == 80, "PsShellsInfo size");
 #endif
 
 #endif /* PARSIP_GPU_H */

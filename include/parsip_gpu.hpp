@@ -190,6 +190,21 @@ struct Welded {
     }
 };
 
+/* The shells of a weld (psgpu_weld_shells, psgpu_group_weld_shells): the connected components
+ * of the welded mesh with their topology, area and volume, and host copies of the indices. */
+struct Shells {
+    PsShellsInfo info{};
+    std::vector<PsShell> shells;        /* info.ctShells, ordered by firstVertex */
+    std::vector<uint32_t> vertexShell;  /* info.ctVertices: shell index of each welded vertex */
+    std::vector<uint32_t> triShell;     /* info.ctTriangles */
+    void resize(const PsShellsInfo& i) {
+        info = i;
+        shells.resize(i.ctShells);
+        vertexShell.resize(i.ctVertices);
+        triShell.resize(i.ctTriangles);
+    }
+};
+
 /* SimdPoly-shaped adapter (PS_HighPerformanceRender.h:15-33) over a device-resident
  * compact mesh: setModel once per edit, run() per frame, mesh() for GL / export. */
 template <class Prims, class Mats, class Ops>
@@ -225,6 +240,22 @@ public:
     }
     /* The same weld left in HBM (valid until the next weld). */
     int weldDevice(PsWeldDevice* out) { return psgpu_weld_device(ctx_.get(), out); }
+    /* The shells of that weld (psgpu_weld_shells).  After weld() or psgpu_weld;
+     * PSGPU_RET_PARAM_ERROR without a weld of the current run (out is left empty). */
+    using Shells = psgpu::Shells;
+    int weldShells(Shells* out) {
+        if (!ctx_.ok()) return ctx_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Shells();
+        PsShellsInfo info;
+        const int rc = psgpu_weld_shells(ctx_.get(), &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_download_weld_shells(ctx_.get(), out->shells.data(), info.ctShells, out->vertexShell.data(),
+                                          out->triShell.data());
+    }
+    /* The same shells left in HBM (valid until the next weld or shells call). */
+    int weldShellsDevice(PsShellsDevice* out) { return psgpu_weld_shells_device(ctx_.get(), out); }
     Context& context() { return ctx_; }
 
 private:
@@ -355,6 +386,21 @@ public:
     }
     /* The same weld left in HBM (valid until the next weld). */
     int weldDevice(PsWeldDevice* out) { return psgpu_group_weld_device(grp_.get(), out); }
+    /* The shells of that weld (psgpu_group_weld_shells): PSGPU_RET_PARAM_ERROR without a weld of
+     * the current run (out is left empty). */
+    using Shells = psgpu::Shells;
+    int weldShells(Shells* out) {
+        if (!grp_.ok()) return grp_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Shells();
+        PsShellsInfo info;
+        const int rc = psgpu_group_weld_shells(grp_.get(), &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_group_download_weld_shells(grp_.get(), out->shells.data(), info.ctShells,
+                                                out->vertexShell.data(), out->triShell.data());
+    }
+    int weldShellsDevice(PsShellsDevice* out) { return psgpu_group_weld_shells_device(grp_.get(), out); }
     const PsMeshInfo& info() const { return info_; }
     const PsSoaBlobPrims& prims() const { return prims_; }
     const PsSoaBlobOps& ops() const { return ops_; }

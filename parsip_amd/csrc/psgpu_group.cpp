@@ -541,6 +541,7 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
     g->weldPart = dstPart;
     WeldState& W = g->weld;
     W.doneSeq = ~0ull;
+    W.shells.valid = false;
     memset(&W.info, 0, sizeof(W.info));
     W.info.ctInputVertices = T.ctVertices;
     W.info.ctTriangles = T.ctTriangles;
@@ -649,6 +650,31 @@ int psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char*
         if (names) names[k] = kGroupWeldPhaseNames[k];
     }
     return n;
+}
+
+// The shells of the group's weld (psgpu_shells.hip), on the welding part's device and the
+// gather stream the weld ran on.
+int psgpu_group_weld_shells(psgpu_group* g, PsShellsInfo* info) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    psgpu_ctx* dst = g->parts[g->weldPart];
+    PSGPU_CHECK(hipSetDevice(dst->device));
+    return shells_run(g->weld, g->gatherStream ? g->gatherStream : dst->stream, dst->timing != 0, info);
+}
+
+int psgpu_group_weld_shells_device(psgpu_group* g, PsShellsDevice* out) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    return shells_device(g->weld, out);
+}
+
+int psgpu_group_download_weld_shells(psgpu_group* g, PsShell* shells, uint32_t capacity, uint32_t* vertexShell,
+                                     uint32_t* triShell) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    PSGPU_CHECK(hipSetDevice(g->parts[g->weldPart]->device));
+    return shells_download(g->weld, shells, capacity, vertexShell, triShell);
+}
+
+int psgpu_group_weld_shells_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
+    return g ? shells_times(g->weld, ms, maxPhases, names) : 0;
 }
 
 int psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCt) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -28,6 +29,27 @@ constexpr size_t kExportPieceBytes = 1u << 20;  // its target piece size
 // psgpu_weld of the context, grown on demand, freed by psgpu_destroy (weld_free).  A group
 // keeps one of its own for psgpu_group_weld, on the gathering part's device (psgpu_group.cpp).
 constexpr int kWeldPhases = 6;  // psgpu_weld_times: the whole weld, then its five launches
+
+// The shells of a welded mesh (psgpu_shells.hip): topology, area and volume of its connected
+// components.  Part of the weld it describes, so a context's weld and a group's both have one;
+// its buffers come with the first psgpu_weld_shells, grow on demand and go with the weld's.
+constexpr int kShellsPhases = 11;  // psgpu_weld_shells_times: the whole call, then its ten steps
+struct ShellsState {
+    unsigned char* table = nullptr;  // open-addressing edge table: keys (8 B a slot), then use counts (8 B a slot)
+    uint32_t* parent = nullptr;      // per welded vertex: union-find parent, then the shell index of a root
+    uint32_t* vertexShell = nullptr; // per welded vertex: its root, then its shell index
+    uint32_t* triShell = nullptr;    // per triangle
+    uint64_t* blockCnt = nullptr;    // per block of vertices: roots, scanned
+    unsigned char* ctl = nullptr;    // error word, largest |coordinate|, the mesh totals
+    unsigned char* acc = nullptr;    // per shell: counts, bounding box keys, the four integer sums
+    PsShell* shells = nullptr;
+    size_t capTable = 0, capV = 0, capT = 0, capBlocks = 0, capCtl = 0, capAcc = 0, capShells = 0;
+    bool valid = false;              // holds the shells of the weld beside it (a new weld clears it)
+    PsShellsInfo info{};
+    hipEvent_t ev[kShellsPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: before the first step, after each
+    float lastMs[kShellsPhases] = {};
+};
+
 struct WeldState {
     unsigned char* table = nullptr;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
     uint32_t* rep = nullptr;         // per input vertex: its representative (the smallest index on its edge)
@@ -43,7 +65,20 @@ struct WeldState {
     PsWeldInfo info{};
     hipEvent_t ev[kWeldPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: around the launches
     float lastMs[kWeldPhases] = {};
+    ShellsState shells;               // psgpu_weld_shells of this weld
 };
+
+// Grow a device buffer to `need` elements (by half again at least); its contents are lost.
+template <typename T>
+hipError_t weld_grow(T*& ptr, size_t& cap, size_t need) {
+    if (need <= cap && ptr) return hipSuccess;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    const size_t n = std::max<size_t>(need, cap + cap / 2);
+    const hipError_t e = hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(T));
+    cap = e == hipSuccess ? n : 0;
+    return e;
+}
 
 }  // namespace psgpu
 
@@ -202,6 +237,18 @@ struct WeldGathered {
     uint32_t V, T;
 };
 int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals);
+// k_weld_scan on its own: blockCnt[0 .. blocks) becomes its exclusive scan, blockCnt[blocks] the
+// total (both 32-bit halves of a word are scanned), enqueued on s.
+void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s);
+// The shells of a weld (psgpu_shells.hip), for a context's weld and a group's alike; the weld's
+// device is current.  shells_run: W holds a finished weld (W.info); blocking on s; `timed`
+// records W.shells.lastMs.  The others serve W.shells once shells_run has succeeded
+// (W.shells.valid).
+int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info);
+int shells_device(const WeldState& W, PsShellsDevice* out);
+int shells_download(const WeldState& W, PsShell* shells, uint32_t capacity, uint32_t* vertexShell, uint32_t* triShell);
+int shells_times(const WeldState& W, float* ms, int maxPhases, const char** names);
+void shells_state_free(ShellsState& S);
 // The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.

@@ -352,17 +352,6 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_map(WeldParams q) {
     }
 }
 
-template <typename T>
-hipError_t weld_grow(T*& ptr, size_t& cap, size_t need) {
-    if (need <= cap && ptr) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    const size_t n = std::max<size_t>(need, cap + cap / 2);
-    const hipError_t e = hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(T));
-    cap = e == hipSuccess ? n : 0;
-    return e;
-}
-
 const char* kWeldPhaseNames[kWeldPhases] = {"weld total", "table fill + k_weld_mark", "k_weld_resolve", "k_weld_scan",
                                             "k_weld_emit", "k_weld_map"};
 
@@ -438,6 +427,7 @@ bool weld_run_ready(const psgpu_ctx* c) {
 }
 
 void weld_state_free(WeldState& W) {
+    shells_state_free(W.shells);
     void* bufs[] = {W.table, W.rep, W.kid, W.map, W.blockCnt, W.pos, W.nrm, W.col, W.tris};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -447,6 +437,14 @@ void weld_state_free(WeldState& W) {
 }
 
 void weld_free(psgpu_ctx* c) { weld_state_free(c->weld); }
+
+void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s) {
+    WeldParams q;
+    memset(&q, 0, sizeof(q));
+    q.blockCnt = blockCnt;
+    q.blocks = blocks;
+    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kWeldBlock), 0, s, q);
+}
 
 int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s) {
     const uint32_t V = c->info.ctVertices;
@@ -504,6 +502,7 @@ int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
     WeldState& W = c->weld;
     const uint32_t V = c->info.ctVertices, T = c->info.ctTriangles;
     W.doneSeq = ~0ull;
+    W.shells.valid = false;
     memset(&W.info, 0, sizeof(W.info));
     W.info.ctInputVertices = V;
     W.info.ctTriangles = T;

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import soa
+from . import meshio, soa
 
 _LIB = None
 _LIVE = weakref.WeakSet()  # contexts / groups closed at interpreter exit (psgpu_destroy
@@ -60,6 +60,29 @@ class PsWeldDevice(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "nrm", "col", "tris", "vertexMap")]
 
 
+class PsShell(ctypes.Structure):
+    _fields_ = [("firstVertex", ctypes.c_uint32), ("ctVertices", ctypes.c_uint32), ("ctTriangles", ctypes.c_uint32),
+                ("ctEdges", ctypes.c_uint32), ("ctOpenEdges", ctypes.c_uint32), ("ctNonManifoldEdges", ctypes.c_uint32),
+                ("ctFlippedEdges", ctypes.c_uint32), ("euler", ctypes.c_int32), ("area", ctypes.c_double),
+                ("volume", ctypes.c_double), ("bboxLo", ctypes.c_float * 3), ("bboxHi", ctypes.c_float * 3)]
+
+
+class PsShellsInfo(ctypes.Structure):
+    _fields_ = [("ctShells", ctypes.c_uint32), ("ctClosedShells", ctypes.c_uint32), ("ctVertices", ctypes.c_uint32),
+                ("ctTriangles", ctypes.c_uint32), ("ctEdges", ctypes.c_uint32), ("ctOpenEdges", ctypes.c_uint32),
+                ("ctNonManifoldEdges", ctypes.c_uint32), ("ctFlippedEdges", ctypes.c_uint32),
+                ("euler", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("area", ctypes.c_double),
+                ("volume", ctypes.c_double), ("bboxLo", ctypes.c_float * 3), ("bboxHi", ctypes.c_float * 3)]
+
+
+class PsShellsDevice(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("shells", "vertexShell", "triShell")]
+
+
+assert ctypes.sizeof(PsShell) == meshio.SHELL_DTYPE.itemsize == 72
+assert ctypes.sizeof(PsShellsInfo) == meshio.SHELLS_INFO_DTYPE.itemsize == 80
+
+
 EXPORTED_SYMBOLS = [
     "psgpu_count_mpus", "psgpu_mpu_dims", "psgpu_prepare_bboxes", "psgpu_translate_blobtree_type",
     "psgpu_tritable", "psgpu_version", "psgpu_create", "psgpu_destroy", "psgpu_device_count",
@@ -78,6 +101,9 @@ EXPORTED_SYMBOLS = [
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
     "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks",
     "psgpu_group_weld", "psgpu_group_weld_device", "psgpu_group_download_weld", "psgpu_group_weld_times",
+    "psgpu_weld_shells", "psgpu_weld_shells_device", "psgpu_download_weld_shells", "psgpu_weld_shells_times",
+    "psgpu_group_weld_shells", "psgpu_group_weld_shells_device", "psgpu_group_download_weld_shells",
+    "psgpu_group_weld_shells_times",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -195,6 +221,14 @@ def load(build_if_missing: bool = True):
         "psgpu_group_weld_device": ([vp, ctypes.POINTER(PsWeldDevice)], i32),
         "psgpu_group_download_weld": ([vp, vp, vp, vp, vp, vp], i32),
         "psgpu_group_weld_times": ([vp, vp, i32, vp], i32),
+        "psgpu_weld_shells": ([vp, ctypes.POINTER(PsShellsInfo)], i32),
+        "psgpu_weld_shells_device": ([vp, ctypes.POINTER(PsShellsDevice)], i32),
+        "psgpu_download_weld_shells": ([vp, vp, ctypes.c_uint32, vp, vp], i32),
+        "psgpu_weld_shells_times": ([vp, vp, i32, vp], i32),
+        "psgpu_group_weld_shells": ([vp, ctypes.POINTER(PsShellsInfo)], i32),
+        "psgpu_group_weld_shells_device": ([vp, ctypes.POINTER(PsShellsDevice)], i32),
+        "psgpu_group_download_weld_shells": ([vp, vp, ctypes.c_uint32, vp, vp], i32),
+        "psgpu_group_weld_shells_times": ([vp, vp, i32, vp], i32),
         "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
         "psgpu_mpu_masks": ([vp, vp, vp, u32], i32),
         "psgpu_live_bricks": ([vp, vp, u32, vp], i32),
@@ -339,6 +373,25 @@ class WeldedMesh:
     tris: np.ndarray        # (T,3) u32 welded vertex ids, the run's triangle order
     vertex_map: np.ndarray  # (V,) u32: welded id of every input vertex
     info: PsWeldInfo
+
+
+def _weld_shells(L, handle, prefix: str) -> meshio.Shells:
+    """psgpu_weld_shells / psgpu_group_weld_shells and the download, as meshio.shells returns them."""
+    info = PsShellsInfo()
+    _check(getattr(L, prefix + "weld_shells")(handle, ctypes.byref(info)), prefix + "weld_shells")
+    shells = np.zeros(info.ctShells, meshio.SHELL_DTYPE)
+    vs = np.zeros(info.ctVertices, np.uint32)
+    ts = np.zeros(info.ctTriangles, np.uint32)
+    _check(getattr(L, prefix + "download_weld_shells")(handle, shells.ctypes.data, info.ctShells, vs.ctypes.data,
+                                                        ts.ctypes.data), prefix + "download_weld_shells")
+    return meshio.Shells(shells, np.frombuffer(bytes(info), meshio.SHELLS_INFO_DTYPE).copy().reshape(()), vs, ts)
+
+
+def _shells_times(fn, handle) -> dict:
+    ms = (ctypes.c_float * 16)()
+    names = (ctypes.c_char_p * 16)()
+    n = fn(handle, ms, 16, names)
+    return {names[i].decode(): ms[i] for i in range(n)}
 
 
 class Polygonizer:
@@ -549,6 +602,22 @@ class Polygonizer:
         n = self._L.psgpu_weld_times(self._ctx, ms, 8, names)
         return {names[i].decode(): ms[i] for i in range(n)}
 
+    def weld_shells(self) -> meshio.Shells:
+        """psgpu_weld_shells on the current weld (``weld()`` or ``weld_info()`` first): the
+        shells of the welded mesh with their topology, area and volume, the same bytes as
+        ``meshio.shells`` of the weld's download."""
+        return _weld_shells(self._L, self._ctx, "psgpu_")
+
+    def weld_shells_device(self) -> PsShellsDevice:
+        """Device pointers of the last ``weld_shells()`` (valid until the next weld or shells call)."""
+        d = PsShellsDevice()
+        _check(self._L.psgpu_weld_shells_device(self._ctx, ctypes.byref(d)), "psgpu_weld_shells_device")
+        return d
+
+    def weld_shells_times(self) -> dict:
+        """hipEvent times (ms) of the last ``weld_shells()`` (OPT_KERNEL_TIMING): the call and its steps."""
+        return _shells_times(self._L.psgpu_weld_shells_times, self._ctx)
+
     def mpu_costs(self) -> np.ndarray:
         """Per-MPU lane-evaluations of the last run (balances ranges across devices)."""
         info = self.finish()
@@ -756,6 +825,20 @@ class Group:
         names = (ctypes.c_char_p * 8)()
         n = self._L.psgpu_group_weld_times(self._g, ms, 8, names)
         return {names[i].decode(): ms[i] for i in range(n)}
+
+    def weld_shells(self) -> meshio.Shells:
+        """psgpu_group_weld_shells on the group's current weld: as ``Polygonizer.weld_shells()``."""
+        return _weld_shells(self._L, self._g, "psgpu_group_")
+
+    def weld_shells_device(self) -> PsShellsDevice:
+        """Device pointers of the last ``weld_shells()`` (valid until the next weld or shells call)."""
+        d = PsShellsDevice()
+        _check(self._L.psgpu_group_weld_shells_device(self._g, ctypes.byref(d)), "psgpu_group_weld_shells_device")
+        return d
+
+    def weld_shells_times(self) -> dict:
+        """hipEvent times (ms) of the last ``weld_shells()`` (OPT_KERNEL_TIMING on the group)."""
+        return _shells_times(self._L.psgpu_group_weld_shells_times, self._g)
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info, _ = self.finish()

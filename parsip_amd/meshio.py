@@ -180,6 +180,174 @@ def open_edge_count(tris) -> int:
     return int((counts == 1).sum())
 
 
+# PsShell / PsShellsInfo (include/parsip_gpu.h), field for field
+SHELL_DTYPE = np.dtype([("firstVertex", "<u4"), ("ctVertices", "<u4"), ("ctTriangles", "<u4"), ("ctEdges", "<u4"),
+                        ("ctOpenEdges", "<u4"), ("ctNonManifoldEdges", "<u4"), ("ctFlippedEdges", "<u4"),
+                        ("euler", "<i4"), ("area", "<f8"), ("volume", "<f8"),
+                        ("bboxLo", "<f4", (3,)), ("bboxHi", "<f4", (3,))])
+SHELLS_INFO_DTYPE = np.dtype([("ctShells", "<u4"), ("ctClosedShells", "<u4"), ("ctVertices", "<u4"),
+                              ("ctTriangles", "<u4"), ("ctEdges", "<u4"), ("ctOpenEdges", "<u4"),
+                              ("ctNonManifoldEdges", "<u4"), ("ctFlippedEdges", "<u4"), ("euler", "<i4"),
+                              ("reserved", "<u4"), ("area", "<f8"), ("volume", "<f8"),
+                              ("bboxLo", "<f4", (3,)), ("bboxHi", "<f4", (3,))])
+assert SHELL_DTYPE.itemsize == 72 and SHELLS_INFO_DTYPE.itemsize == 80
+
+
+@dataclass
+class Shells:
+    """What `shells` returns (and, from the device, `gpu.Polygonizer.weld_shells`)."""
+    shells: np.ndarray        # (ctShells,) SHELL_DTYPE, ordered by firstVertex
+    info: np.ndarray          # 0-d SHELLS_INFO_DTYPE: the whole mesh
+    vertex_shell: np.ndarray  # (V,) u32: shell index of each vertex
+    tri_shell: np.ndarray     # (T,) u32
+
+    def tobytes(self) -> bytes:
+        return b"".join(np.ascontiguousarray(a).tobytes()
+                        for a in (self.shells, self.info, self.vertex_shell, self.tri_shell))
+
+
+def shell_scales(pos, n_triangles: int):
+    """The fixed-point exponents (eA, eV) of the shells' area and volume sums (parsip_gpu.h,
+    "Reproducible measures"): M the largest |coordinate|, k the smallest integer with M < 2^k
+    (0 for M = 0), L = ceil(log2(max(T, 2)))."""
+    p = np.ascontiguousarray(pos, np.float32)
+    big = float(np.abs(p).max()) if p.size else 0.0
+    k = int(np.frexp(big)[1]) if big > 0.0 else 0   # big = m 2^k, 0.5 <= m < 1
+    ell = (max(int(n_triangles), 2) - 1).bit_length()
+    return 58 - 2 * k - ell, 58 - 3 * k - ell
+
+
+def shell_terms(pos, tris):
+    """Per triangle, A2 (twice its area) and V6 (six times its signed volume towards the
+    origin) in float64 from the float32 positions, in the header's written-out order."""
+    p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3).astype(np.float64)
+    t = np.asarray(tris).astype(np.int64).reshape(-1, 3)
+    a, b, c = p[t[:, 0]], p[t[:, 1]], p[t[:, 2]]
+    ax, ay, az = a[:, 0], a[:, 1], a[:, 2]
+    bx, by, bz = b[:, 0], b[:, 1], b[:, 2]
+    cx, cy, cz = c[:, 0], c[:, 1], c[:, 2]
+    ux, uy, uz = bx - ax, by - ay, bz - az
+    vx, vy, vz = cx - ax, cy - ay, cz - az
+    nx, ny, nz = uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx
+    a2 = np.sqrt(nx * nx + ny * ny + nz * nz)
+    v6 = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx)
+    return a2, v6
+
+
+def shell_split(x, e: int):
+    """x 2^e as (hi, lo) int64: hi = floor(y), lo = floor((y - hi) 2^30)."""
+    y = np.ldexp(np.asarray(x, np.float64), e)
+    hi = np.floor(y)
+    lo = np.floor((y - hi) * float(1 << 30))
+    return hi.astype(np.int64), lo.astype(np.int64)
+
+
+def shell_join(hi, lo, e: int, div: float):
+    """The value of two accumulators: (ldexp(hi, -e) + ldexp(lo, -e - 30)) / div."""
+    return (np.ldexp(np.asarray(hi, np.int64).astype(np.float64), -e) +
+            np.ldexp(np.asarray(lo, np.int64).astype(np.float64), -e - 30)) / div
+
+
+def _float_order(a):
+    """float32 -> u32 keys that order as the floats do, -0 below +0 (the device's min / max)."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _float_unorder(k):
+    k = np.asarray(k, np.uint32)
+    return np.where(k >> 31 != 0, k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+def _components(n: int, a, b) -> np.ndarray:
+    """Smallest vertex id of the connected component of each of n vertices under edges a-b."""
+    lab = np.arange(n, dtype=np.int64)
+    while len(a):
+        new = lab.copy()
+        la, lb = lab[a], lab[b]
+        m = np.minimum(la, lb)
+        np.minimum.at(new, la, m)   # hook the larger root under the smaller
+        np.minimum.at(new, lb, m)
+        while True:                 # flatten
+            nxt = new[new]
+            if np.array_equal(nxt, new):
+                break
+            new = nxt
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return lab
+
+
+def shells(pos, tris=None) -> Shells:
+    """The shells (connected components) of an indexed mesh with their topology, area and
+    volume: the host form of psgpu_weld_shells, same rule (parsip_gpu.h), same bytes.
+    ``shells(mesh)`` takes a TriMesh or a gpu.WeldedMesh, ``shells(pos, tris)`` the arrays."""
+    if tris is None:
+        pos, tris = pos.pos, pos.tris
+    p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    t = np.asarray(tris).astype(np.int64).reshape(-1, 3)
+    V, T = len(p), len(t)
+    if T and (t.min() < 0 or t.max() >= V):
+        raise ValueError("a triangle names a vertex the mesh does not have")
+    info = np.zeros((), SHELLS_INFO_DTYPE)
+    if V == 0:
+        return Shells(np.zeros(0, SHELL_DTYPE), info, np.zeros(0, np.uint32), np.zeros(0, np.uint32))
+    root = _components(V, np.concatenate([t[:, 0], t[:, 1]]), np.concatenate([t[:, 1], t[:, 2]]))
+    first = np.flatnonzero(root == np.arange(V))
+    S = len(first)
+    index = np.zeros(V, np.int64)
+    index[first] = np.arange(S)
+    vs = index[root]
+    ts = vs[t[:, 0]]
+    out = np.zeros(S, SHELL_DTYPE)
+    out["firstVertex"] = first
+    out["ctVertices"] = np.bincount(vs, minlength=S)
+    out["ctTriangles"] = np.bincount(ts, minlength=S)
+    # edges: uses a -> b of every triangle, none for a == b
+    ea = np.concatenate([t[:, 0], t[:, 1], t[:, 2]])
+    eb = np.concatenate([t[:, 1], t[:, 2], t[:, 0]])
+    use = ea != eb
+    ea, eb = ea[use], eb[use]
+    key, inv = np.unique(np.minimum(ea, eb) << 32 | np.maximum(ea, eb), return_inverse=True)
+    inv = inv.reshape(-1)
+    f = np.bincount(inv[ea < eb], minlength=len(key))
+    b = np.bincount(inv[ea > eb], minlength=len(key))
+    es = vs[key >> 32]
+    out["ctEdges"] = np.bincount(es, minlength=S)
+    out["ctOpenEdges"] = np.bincount(es[f + b == 1], minlength=S)
+    out["ctFlippedEdges"] = np.bincount(es[(f + b == 2) & (f != b)], minlength=S)
+    out["ctNonManifoldEdges"] = np.bincount(es[f + b >= 3], minlength=S)
+    out["euler"] = (out["ctVertices"].astype(np.int64) - out["ctEdges"] + out["ctTriangles"]).astype(np.int32)
+    # measures: exact integer sums of the split terms
+    e_a, e_v = shell_scales(p, T)
+    a2, v6 = shell_terms(p, t)
+    acc = np.zeros((4, S), np.int64)
+    for row, (x, e) in enumerate(((a2, e_a), (v6, e_v))):
+        hi, lo = shell_split(x, e)
+        np.add.at(acc[2 * row], ts, hi)
+        np.add.at(acc[2 * row + 1], ts, lo)
+    out["area"] = shell_join(acc[0], acc[1], e_a, 2.0)
+    out["volume"] = shell_join(acc[2], acc[3], e_v, 6.0)
+    keys = _float_order(p)
+    lo_k = np.full((S, 3), 0xFFFFFFFF, np.uint32)
+    hi_k = np.zeros((S, 3), np.uint32)
+    np.minimum.at(lo_k, vs, keys)
+    np.maximum.at(hi_k, vs, keys)
+    out["bboxLo"], out["bboxHi"] = _float_unorder(lo_k), _float_unorder(hi_k)
+    closed = ((out["ctOpenEdges"] == 0) & (out["ctFlippedEdges"] == 0) & (out["ctNonManifoldEdges"] == 0) &
+              (out["ctTriangles"] > 0))
+    info["ctShells"], info["ctClosedShells"] = S, int(closed.sum())
+    for name in ("ctVertices", "ctTriangles", "ctEdges", "ctOpenEdges", "ctNonManifoldEdges", "ctFlippedEdges"):
+        info[name] = out[name].astype(np.int64).sum()
+    info["euler"] = int(info["ctVertices"]) - int(info["ctEdges"]) + int(info["ctTriangles"])
+    tot = acc.sum(axis=1)
+    info["area"] = shell_join(tot[0], tot[1], e_a, 2.0)
+    info["volume"] = shell_join(tot[2], tot[3], e_v, 6.0)
+    info["bboxLo"], info["bboxHi"] = _float_unorder(lo_k.min(axis=0)), _float_unorder(hi_k.max(axis=0))
+    return Shells(out, info, vs.astype(np.uint32), ts.astype(np.uint32))
+
+
 def _fmt(a) -> str:
     return " ".join(f"{float(x):.9g}" for x in a)
 

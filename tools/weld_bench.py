@@ -19,6 +19,13 @@ before: Group.download() + meshio.weld.  Output of --parts 1, 2 and 8 committed 
 profiles/group_weld_c3.txt (DESIGN.md §6 "Weld of a group").
 
     python3 tools/weld_bench.py [CONFIG] --parts N
+
+With --shells the shells of the weld are timed (psgpu_weld_shells: hipEvents through
+psgpu_weld_shells_times, the whole call and each step, median of 20 after 5 warm-ups), beside
+the weld re-measured in the same process and the host route download of the weld +
+meshio.shells.  Output committed as profiles/shells_c3.txt (DESIGN.md §6 "Shells").
+
+    python3 tools/weld_bench.py [CONFIG] --shells
 """
 import argparse
 import os
@@ -29,7 +36,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-from parsip_amd import gpu, meshio, synth  # noqa: E402
+from parsip_amd import gpu, meshio, soa, synth  # noqa: E402
 
 WARMUP, REPS, HOST_REPS = 5, 20, 3
 
@@ -104,11 +111,72 @@ def group_main(name, parts):
     poly.close()
 
 
+def shells_main(name):
+    model, cs, _ = synth.make_config(name)
+    poly = gpu.Polygonizer(0)
+    poly.set_option(gpu.OPT_KERNEL_TIMING, 1)
+    poly.set_model(model)
+    info = poly.run(cs)
+    print(f"{name}: cellsize {cs}, {info.ctMPUs} MPUs, {info.ctVertices} vertices, {info.ctTriangles} triangles")
+    rows, wall, winfo = timed_welds(poly.weld_info, poly.weld_times)
+    print(f"device weld, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms):")
+    print_phases(rows)
+    print(f"  {'psgpu_weld call, wall':28s} {statistics.median(wall):8.4f}")
+    weld_ms = statistics.median([r["weld total"] for r in rows])
+
+    L = gpu.load()
+    sinfo = gpu.PsShellsInfo()
+
+    def shells_info():
+        rc = L.psgpu_weld_shells(poly._ctx, sinfo)
+        assert rc == soa.RET_SUCCESS, rc
+        return sinfo
+
+    rows, wall, _ = timed_welds(shells_info, poly.weld_shells_times)
+    print(f"device shells, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms; the total and the "
+          "k_shells_ids row include the host's read of the shell count between the two halves):")
+    print_phases(rows)
+    print(f"  {'psgpu_weld_shells call, wall':28s} {statistics.median(wall):8.4f}")
+    med = {ph: statistics.median([r[ph] for r in rows]) for ph in rows[0]}
+    dev_ms = med["shells total"]
+    top = max((ph for ph in med if ph != "shells total"), key=lambda ph: med[ph])
+    print(f"  largest phase: {top} ({med[top]:.4f} ms, {100 * med[top] / dev_ms:.0f} % of the total)")
+    acc = med["k_shells_vertices"] + med["k_shells_edge_class"] + med["k_shells_triangles"]
+    print(f"  the three accumulate kernels: {acc:.4f} ms ({100 * acc / dev_ms:.0f} % of the total)")
+    sh = poly.weld_shells()
+    i = sh.info
+    print(f"shells: {i['ctShells']} ({i['ctClosedShells']} closed), V {i['ctVertices']} T {i['ctTriangles']} "
+          f"E {i['ctEdges']}, open {i['ctOpenEdges']}, non-manifold {i['ctNonManifoldEdges']}, "
+          f"flipped {i['ctFlippedEdges']}, euler {i['euler']}, area {float(i['area']):.12g}, "
+          f"volume {float(i['volume']):.12g}")
+    for s in sh.shells[:8]:
+        print(f"  shell first vertex {s['firstVertex']}: V {s['ctVertices']} T {s['ctTriangles']} E {s['ctEdges']} "
+              f"open {s['ctOpenEdges']} euler {s['euler']} area {float(s['area']):.9g} volume {float(s['volume']):.9g}")
+
+    ts, ref = [], None
+    for _ in range(HOST_REPS):
+        t0 = time.perf_counter()
+        w = poly.weld()
+        t1 = time.perf_counter()
+        ref = meshio.shells(w.pos, w.tris)
+        ts.append(((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
+    dl_ms, host_ms = (statistics.median(c) for c in zip(*ts))
+    print(f"host route, median of {HOST_REPS} (wall, ms):")
+    print(f"  {'weld() (weld + download)':36s} {dl_ms:10.2f}")
+    print(f"  {'weld() + meshio.shells':36s} {host_ms:10.2f}")
+    print(f"device shells == meshio.shells: {sh.tobytes() == ref.tobytes()}")
+    print(f"shells / weld on the device: {dev_ms / weld_ms:.2f}x; host route / device shells: {host_ms / dev_ms:.0f}x")
+    poly.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", nargs="?", default="C3")
     ap.add_argument("--parts", type=int, default=0, help="run as a Group of N parts on device 0 and time psgpu_group_weld")
+    ap.add_argument("--shells", action="store_true", help="time psgpu_weld_shells on the weld")
     args = ap.parse_args()
+    if args.shells:
+        return shells_main(args.config)
     if args.parts > 0:
         return group_main(args.config, args.parts)
     name = args.config
