@@ -401,6 +401,10 @@ int  psgpu_mpu_masks(psgpu_ctx* ctx, uint8_t* queued, uint64_t* masks, uint32_t 
  * their number (0 when the run took no sieve: PSGPU_LAUNCH_SIEVE), bricks (may be null) 3 words
  * per brick, its lattice brick coordinates (x, y, z: MPU coordinates / 2). */
 int  psgpu_live_bricks(psgpu_ctx* ctx, uint32_t* bricks, uint32_t capacity, uint32_t* count);
+/* Device memory the library holds at this moment, in bytes, over every context, group, comm
+ * and compatibility context of the process (pinned host memory is not counted).  Exact, unlike
+ * a device's free memory, which other processes change: a leak test compares two readings. */
+uint64_t psgpu_debug_device_bytes(void);
 /* PrintThreadResults (PS_Polygonizer.h:393, body .cpp:414-428, counters .cpp:443-469).
  * The reference keeps one (processed, crossed) MPU count pair per TBB worker that ran an
  * MPU, accumulated over every Polygonize of the process.  Here the worker is a device

@@ -58,13 +58,12 @@ struct psgpu_group {
     // gathered mesh (psgpu_group_gather) on one part's device
     int gatherPart = -1;
     hipStream_t gatherStream = nullptr;
-    float *gPos = nullptr, *gNrm = nullptr, *gCol = nullptr;
-    uint32_t* gTris = nullptr;
-    uint64_t* gOffs = nullptr;
-    size_t gCapV = 0, gCapT = 0, gCapM = 0;
+    DevBuf<float> gPos, gNrm, gCol;
+    DevBuf<uint32_t> gTris;
+    DevBuf<uint64_t> gOffs;
     // one rank's parts summed for the RCCL exchange (psgpu_comm_exchange_group)
     std::vector<hipEvent_t> done;
-    uint32_t* sumTotals = nullptr;
+    DevBuf<uint32_t> sumTotals;        // on the first part's device
     // psgpu_group_weld: runSeq counts whatever supersedes the group's run or its split
     // (set_model, polygonize, set_split, a capacity change), as psgpu_ctx::runSeq does for a
     // context; partSeq is each part's own runSeq when the group's finish collected it
@@ -73,10 +72,8 @@ struct psgpu_group {
     // the welded mesh on one part's device: allocated by the first weld, grown on demand
     int weldPart = -1;
     WeldState weld;                    // doneSeq: the group's runSeq of the welded run
-    uint64_t* gEdge = nullptr;         // the gathered vertices' edge ids, beside the gathered mesh
-    size_t capEdge = 0;
-    std::vector<uint64_t*> partEdge;   // each part's edge ids on its own device (k_weld_edges)
-    std::vector<size_t> partEdgeCap;
+    DevBuf<uint64_t> gEdge;            // the gathered vertices' edge ids, beside the gathered mesh
+    std::vector<DevBuf<uint64_t>> partEdge;  // each part's edge ids on its own device (k_weld_edges)
     std::vector<hipEvent_t> partEdgeEv;  // ... and the event the gather stream waits for
     hipEvent_t weldEv[kGroupWeldPhases] = {};
     float weldMs[kGroupWeldPhases] = {};
@@ -88,15 +85,13 @@ void free_gather(psgpu_group* g) {
     if (g->gatherPart < 0) return;
     (void)hipSetDevice(g->parts[g->gatherPart]->device);
     if (g->gatherStream) (void)hipStreamSynchronize(g->gatherStream);
-    void* bufs[] = {g->gPos, g->gNrm, g->gCol, g->gTris, g->gOffs};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
+    g->gPos.release();
+    g->gNrm.release();
+    g->gCol.release();
+    g->gTris.release();
+    g->gOffs.release();
     if (g->gatherStream) (void)hipStreamDestroy(g->gatherStream);
-    g->gPos = g->gNrm = g->gCol = nullptr;
-    g->gTris = nullptr;
-    g->gOffs = nullptr;
     g->gatherStream = nullptr;
-    g->gCapV = g->gCapT = g->gCapM = 0;
     g->gatherPart = -1;
 }
 
@@ -104,7 +99,7 @@ void free_weld(psgpu_group* g) {
     if (g->weldPart >= 0) {
         (void)hipSetDevice(g->parts[g->weldPart]->device);
         weld_state_free(g->weld);  // (hipFree waits for the device)
-        if (g->gEdge) (void)hipFree(g->gEdge);
+        g->gEdge.release();
         for (hipEvent_t& e : g->weldEv) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
@@ -113,15 +108,11 @@ void free_weld(psgpu_group* g) {
     for (size_t p = 0; p < g->partEdge.size(); ++p) {
         if (!g->partEdge[p] && !g->partEdgeEv[p]) continue;
         (void)hipSetDevice(g->parts[p]->device);
-        if (g->partEdge[p]) (void)hipFree(g->partEdge[p]);
+        g->partEdge[p].release();
         if (g->partEdgeEv[p]) (void)hipEventDestroy(g->partEdgeEv[p]);
     }
     g->partEdge.clear();
-    g->partEdgeCap.clear();
     g->partEdgeEv.clear();
-    g->weld = WeldState{};
-    g->gEdge = nullptr;
-    g->capEdge = 0;
     g->weldPart = -1;
 }
 
@@ -255,7 +246,7 @@ void psgpu_group_destroy(psgpu_group* g) {
     if (!g->parts.empty()) (void)hipSetDevice(g->parts[0]->device);
     for (hipEvent_t e : g->done)
         if (e) (void)hipEventDestroy(e);
-    if (g->sumTotals) (void)hipFree(g->sumTotals);
+    g->sumTotals.release();
     for (psgpu_ctx* c : g->parts) psgpu_destroy(c);
     delete g;
 }
@@ -458,20 +449,11 @@ static int gather_enqueue(psgpu_group* g, int dstPart, const PsMeshInfo& T, hipE
     if (before) PSGPU_CHECK(hipEventRecord(before, g->gatherStream));
     const size_t V = std::max<size_t>(T.ctVertices, 1), Tn = std::max<size_t>(T.ctTriangles, 1),
                  M = (size_t)T.ctMPUs + 1;
-    auto grow = [](auto*& ptr, size_t& cap, size_t need, size_t elt) -> hipError_t {
-        if (need <= cap && ptr) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), need * elt);
-        cap = e == hipSuccess ? need : 0;
-        return e;
-    };
-    size_t capV2 = g->gCapV, capV3 = g->gCapV;
-    PSGPU_CHECK(grow(g->gPos, g->gCapV, V, 12));
-    PSGPU_CHECK(grow(g->gNrm, capV2, V, 12));
-    PSGPU_CHECK(grow(g->gCol, capV3, V, 12));
-    PSGPU_CHECK(grow(g->gTris, g->gCapT, Tn, 12));
-    PSGPU_CHECK(grow(g->gOffs, g->gCapM, M, 8));
+    PSGPU_CHECK(g->gPos.reserve(V * 3, Growth::Exact));
+    PSGPU_CHECK(g->gNrm.reserve(V * 3, Growth::Exact));
+    PSGPU_CHECK(g->gCol.reserve(V * 3, Growth::Exact));
+    PSGPU_CHECK(g->gTris.reserve(Tn * 3, Growth::Exact));
+    PSGPU_CHECK(g->gOffs.reserve(M, Growth::Exact));
     hipStream_t s = g->gatherStream;
     uint64_t mBase = 0;
     for (size_t p = 0; p < g->parts.size(); ++p) {
@@ -552,26 +534,16 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
         return PSGPU_RET_SUCCESS;
     }
     if (g->partEdge.size() != n) {
-        g->partEdge.assign(n, nullptr);
-        g->partEdgeCap.assign(n, 0);
+        g->partEdge.resize(n);  // (empty before: free_weld clears both)
         g->partEdgeEv.assign(n, nullptr);
     }
-    auto grow = [](uint64_t*& ptr, size_t& cap, size_t need) -> hipError_t {
-        if (need <= cap && ptr) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        const size_t m = std::max(need, cap + cap / 2);
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), m * sizeof(uint64_t));
-        cap = e == hipSuccess ? m : 0;
-        return e;
-    };
     // the parts' edge ids, each on its own device and stream: devices work side by side
     for (size_t p = 0; p < n; ++p) {
         psgpu_ctx* c = g->parts[p];
         if (!g->info[p].ctVertices) continue;
         rc = set_device(c);
         if (rc != PSGPU_RET_SUCCESS) return rc;
-        PSGPU_CHECK(grow(g->partEdge[p], g->partEdgeCap[p], g->info[p].ctVertices));
+        PSGPU_CHECK(g->partEdge[p].reserve(g->info[p].ctVertices, Growth::ByHalf));
         if (!g->partEdgeEv[p]) PSGPU_CHECK(hipEventCreateWithFlags(&g->partEdgeEv[p], hipEventDisableTiming));
         rc = weld_edges(c, g->partEdge[p], c->stream);
         if (rc != PSGPU_RET_SUCCESS) return rc;
@@ -583,7 +555,7 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
     if (timed)
         for (hipEvent_t& e : g->weldEv)
             if (!e) PSGPU_CHECK(hipEventCreate(&e));
-    PSGPU_CHECK(grow(g->gEdge, g->capEdge, T.ctVertices));
+    PSGPU_CHECK(g->gEdge.reserve(T.ctVertices, Growth::ByHalf));
     rc = gather_enqueue(g, dstPart, T, timed ? g->weldEv[0] : nullptr);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     hipStream_t s = g->gatherStream;
@@ -619,27 +591,14 @@ static bool group_welded(const psgpu_group* g) {
 
 int psgpu_group_weld_device(psgpu_group* g, PsWeldDevice* out) {
     if (!out || !group_welded(g)) return PSGPU_RET_PARAM_ERROR;
-    const WeldState& W = g->weld;
-    out->pos = W.pos;
-    out->nrm = W.nrm;
-    out->col = W.col;
-    out->tris = W.tris;
-    out->vertexMap = W.map;
-    return PSGPU_RET_SUCCESS;
+    return weld_device(g->weld, out);
 }
 
 int psgpu_group_download_weld(psgpu_group* g, float* pos, float* nrm, float* col, uint32_t* tris,
                               uint32_t* vertexMap) {
     if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
     PSGPU_CHECK(hipSetDevice(g->parts[g->weldPart]->device));
-    const WeldState& W = g->weld;
-    const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
-    if (pos && V) PSGPU_CHECK(hipMemcpy(pos, W.pos, V * 12, hipMemcpyDeviceToHost));
-    if (nrm && V) PSGPU_CHECK(hipMemcpy(nrm, W.nrm, V * 12, hipMemcpyDeviceToHost));
-    if (col && V) PSGPU_CHECK(hipMemcpy(col, W.col, V * 12, hipMemcpyDeviceToHost));
-    if (tris && T) PSGPU_CHECK(hipMemcpy(tris, W.tris, T * 12, hipMemcpyDeviceToHost));
-    if (vertexMap && Vin) PSGPU_CHECK(hipMemcpy(vertexMap, W.map, Vin * 4, hipMemcpyDeviceToHost));
-    return PSGPU_RET_SUCCESS;
+    return weld_download(g->weld, pos, nrm, col, tris, vertexMap);
 }
 
 int psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
@@ -730,11 +689,11 @@ int psgpu_group_polygonize_mpus(psgpu_group* g, float cellsize, const PsSoaBlobP
 struct psgpu_comm {
     ncclComm_t comm = nullptr;
     int nranks = 0, rank = 0, device = 0;
-    uint32_t* gathered = nullptr;      // device: nranks x 8 words
-    uint32_t* hostGathered = nullptr;  // pinned copy
-    uint32_t* flag = nullptr;          // device: the "some rank re-ran" all-reduce word, then a
+    DevBuf<uint32_t> gathered;         // device: nranks x 8 words
+    PinnedBuf<uint32_t> hostGathered;  // pinned copy
+    DevBuf<uint32_t> flag;             // device: the "some rank re-ran" all-reduce word, then a
                                        // constant 2 (a failed rank's contribution, no copy needed)
-    uint32_t* hostFlag = nullptr;      // pinned
+    PinnedBuf<uint32_t> hostFlag;      // pinned
     bool pending = false;
     bool reexchanged = false;          // the last result needed the second exchange
     psgpu_ctx* ctx = nullptr;          // the context whose run was exchanged
@@ -770,10 +729,10 @@ int psgpu_comm_create(psgpu_ctx* ctx, const uint8_t id[PSGPU_COMM_ID_BYTES], int
     memcpy(&u, id, sizeof(u));
     rc = nccl_fail(ncclCommInitRank(&m->comm, nranks, u, rank), "ncclCommInitRank");
     if (rc == PSGPU_RET_SUCCESS &&
-        (hipMalloc(&m->gathered, (size_t)nranks * 8 * sizeof(uint32_t)) != hipSuccess ||
-         hipHostMalloc(&m->hostGathered, (size_t)nranks * 8 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-         hipMalloc(&m->flag, 2 * sizeof(uint32_t)) != hipSuccess ||
-         hipHostMalloc(&m->hostFlag, 9 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess))
+        (m->gathered.reserve((size_t)nranks * 8, Growth::Exact) != hipSuccess ||
+         m->hostGathered.reserve((size_t)nranks * 8, hipHostMallocDefault) != hipSuccess ||
+         m->flag.reserve(2, Growth::Exact) != hipSuccess ||
+         m->hostFlag.reserve(9, hipHostMallocDefault) != hipSuccess))
         rc = PSGPU_RET_DEVICE_ERROR;
     if (rc == PSGPU_RET_SUCCESS) {
         const uint32_t failWords[2] = {0u, 2u};
@@ -792,11 +751,7 @@ void psgpu_comm_destroy(psgpu_comm* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->comm) (void)ncclCommDestroy(m->comm);
-    if (m->gathered) (void)hipFree(m->gathered);
-    if (m->hostGathered) (void)hipHostFree(m->hostGathered);
-    if (m->flag) (void)hipFree(m->flag);
-    if (m->hostFlag) (void)hipHostFree(m->hostFlag);
-    delete m;
+    delete m;  // with its buffers
 }
 
 // Enqueue the exchange of the context's last polygonization (its k_finish totals) on the
@@ -830,7 +785,7 @@ int psgpu_comm_exchange_group(psgpu_comm* m, psgpu_group* g) {
         g->done.assign(g->parts.size(), nullptr);
         for (hipEvent_t& e : g->done) PSGPU_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    if (!g->sumTotals) PSGPU_CHECK(hipMalloc(&g->sumTotals, 8 * sizeof(uint32_t)));
+    PSGPU_CHECK(g->sumTotals.reserve(8, Growth::Exact));
     hipStream_t s0 = c0->runStream ? c0->runStream : c0->stream;
     TotalsParts tp{};
     tp.n = (int)g->parts.size();

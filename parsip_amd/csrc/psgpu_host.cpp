@@ -384,17 +384,6 @@ void lattice_dims(float cs, const PsVec3f& lo, const PsVec3f& hi, uint32_t d[3])
     }
 }
 
-template <typename T>
-hipError_t grow(T*& ptr, size_t& cap, size_t need) {
-    if (need <= cap && ptr) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    size_t n = std::max<size_t>(need, cap + cap / 2);
-    hipError_t e = hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(T));
-    cap = e == hipSuccess ? n : 0;
-    return e;
-}
-
 const char* kKernelNames[kNumKernels] = {"k_precheck", "k_mpu", "k_vertex", "k_finish"};
 
 }  // namespace
@@ -449,26 +438,26 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
     // k_front's 8 sub-queues: a block's bricks x 8 MPUs for every 8th k_precheck block
     const size_t fq = 8 * front_cap(brick_count(c));
     const size_t nq = std::max<size_t>((size_t)c->pShardCap * kShards, fq);
-    PSGPU_CHECK(grow(c->pq, c->capList, nq));
-    PSGPU_CHECK(grow(c->pqMask, c->capPqMask, nq * 4));  // culling + op-inside mask per entry
-    PSGPU_CHECK(grow(c->liveList, c->capLive, brick_count(c)));  // k_sieve: at most every brick
-    if (fq > c->capFq) {  // ready words start at 0: no run's tag
-        PSGPU_CHECK(grow(c->fqReady, c->capFq, fq));
-        PSGPU_CHECK(hipMemset(c->fqReady, 0, c->capFq * sizeof(uint32_t)));
-    }
-    PSGPU_CHECK(grow(c->counts, c->capCounts, n));
-    PSGPU_CHECK(grow(c->passed, c->capPassed, n));
-    PSGPU_CHECK(grow(c->mpuMasks, c->capMasks, 4 * n));
-    PSGPU_CHECK(grow(c->offs, c->capOff, n + 1));
-    PSGPU_CHECK(grow(c->vk, c->capVk, (size_t)c->vShardCap * kShards));
-    PSGPU_CHECK(grow(c->vp, c->capVp, (size_t)c->vShardCap * kShards));
-    PSGPU_CHECK(grow(c->tq, c->capTq, (size_t)c->tShardCap * kShards));
-    size_t capV2 = c->capV, capV3 = c->capV;
-    PSGPU_CHECK(grow(c->pos, c->capV, (size_t)c->vcap * 3));
-    PSGPU_CHECK(grow(c->nrm, capV2, (size_t)c->vcap * 3));
-    PSGPU_CHECK(grow(c->col, capV3, (size_t)c->vcap * 3));
-    PSGPU_CHECK(grow(c->tris, c->capT, (size_t)c->tcap * 3));
-    if (c->mpuTicksOpt) PSGPU_CHECK(grow(c->mpuTicks, c->capTicks, 4 * n));
+    constexpr Growth H = Growth::ByHalf;
+    PSGPU_CHECK(c->pq.reserve(nq, H));
+    PSGPU_CHECK(c->pqMask.reserve(nq * 4, H));  // culling + op-inside mask per entry
+    PSGPU_CHECK(c->liveList.reserve(brick_count(c), H));  // k_sieve: at most every brick
+    bool fresh = false;
+    if (fq) PSGPU_CHECK(c->fqReady.reserve(fq, H, &fresh));
+    if (fresh)  // ready words start at 0: no run's tag
+        PSGPU_CHECK(hipMemset(c->fqReady, 0, c->fqReady.cap * sizeof(uint32_t)));
+    PSGPU_CHECK(c->counts.reserve(n, H));
+    PSGPU_CHECK(c->passed.reserve(n, H));
+    PSGPU_CHECK(c->mpuMasks.reserve(4 * n, H));
+    PSGPU_CHECK(c->offs.reserve(n + 1, H));
+    PSGPU_CHECK(c->vk.reserve((size_t)c->vShardCap * kShards, H));
+    PSGPU_CHECK(c->vp.reserve((size_t)c->vShardCap * kShards, H));
+    PSGPU_CHECK(c->tq.reserve((size_t)c->tShardCap * kShards, H));
+    PSGPU_CHECK(c->pos.reserve((size_t)c->vcap * 3, H));
+    PSGPU_CHECK(c->nrm.reserve((size_t)c->vcap * 3, H));
+    PSGPU_CHECK(c->col.reserve((size_t)c->vcap * 3, H));
+    PSGPU_CHECK(c->tris.reserve((size_t)c->tcap * 3, H));
+    if (c->mpuTicksOpt) PSGPU_CHECK(c->mpuTicks.reserve(4 * n, H));
     return PSGPU_RET_SUCCESS;
 }
 
@@ -820,7 +809,7 @@ void reset_run_state(psgpu_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipMemcpy(c->ctr, init, sizeof(init), hipMemcpyHostToDevice);
     (void)hipMemset(c->scanStatus, 0, 2 * kScanMaxBlocks * sizeof(uint64_t));
-    if (c->fqReady) (void)hipMemset(c->fqReady, 0, c->capFq * sizeof(uint32_t));  // the epochs restart at 0
+    if (c->fqReady) (void)hipMemset(c->fqReady, 0, c->fqReady.cap * sizeof(uint32_t));  // the epochs restart at 0
     (void)hipDeviceSynchronize();
     c->parity = 0;
     c->epochRuns = 0;
@@ -977,6 +966,8 @@ int psgpu_prepare_bboxes(float cellsize, PsSoaBlobPrims* P, PsSoaBoxMatrices* BM
     return PSGPU_RET_SUCCESS;
 }
 
+uint64_t psgpu_debug_device_bytes(void) { return g_deviceBytes.load(); }
+
 int psgpu_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1003,14 +994,15 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
     // the set-up copies run on the null stream BEFORE this context's stream exists: a process's
     // first stream created ahead of the null stream's first use shares its hardware queue
     // (tools/queue_probe.py: with 4 engines, the engine on that stream slowed every step ~25%)
-    if (hipMalloc(&c->dTables, sizeof(CubeTablesDev)) != hipSuccess ||
+    constexpr Growth X = Growth::Exact;
+    if (c->dTables.reserve(1, X) != hipSuccess ||
         hipMemcpy(c->dTables, &tabHost, sizeof(CubeTablesDev), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&c->dModel, sizeof(DevModel)) != hipSuccess ||
-        hipMalloc(&c->ctr, 2 * sizeof(DevCounters)) != hipSuccess ||
-        hipMalloc(&c->totals, 16 * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&c->scanStatus, 2 * kScanMaxBlocks * sizeof(uint64_t)) != hipSuccess ||
+        c->dModel.reserve(1, X) != hipSuccess ||
+        c->ctr.reserve(2, X) != hipSuccess ||
+        c->totals.reserve(16, X) != hipSuccess ||
+        c->scanStatus.reserve(2 * kScanMaxBlocks, X) != hipSuccess ||
         hipMemset(c->scanStatus, 0, 2 * kScanMaxBlocks * sizeof(uint64_t)) != hipSuccess ||
-        hipHostMalloc(&c->hostCtr, sizeof(DevCounters), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        c->hostCtr.reserve(1, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hostCtrDev), c->hostCtr, 0) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1072,19 +1064,12 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->jit.reset();
     c->jit1.reset();
     weld_free(c);
-    void* bufs[] = {c->dModel, c->dTables, c->pq, c->pqMask, c->liveList, c->fqReady, c->scanStatus, c->counts, c->passed, c->mpuMasks, c->offs, c->vk, c->vp, c->tq,
-                    c->pos, c->nrm, c->col, c->tris, c->ctr, c->totals, c->stamps, c->spans, c->mpuTicks};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->hostCtr) (void)hipHostFree(c->hostCtr);
-    if (c->clockProbe) (void)hipHostFree(c->clockProbe);
-    if (c->hostStage) (void)hipHostFree(c->hostStage);
     for (int i = 0; i <= kNumKernels; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t e : c->exportEv)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // its buffers go with it, on the device made current above
 }
 
 int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
@@ -1103,11 +1088,13 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
         if (c->pending) (void)hipStreamSynchronize(c->runStream);
         set_pending(c, false);
         c->seenV = c->seenT = c->seenShardV = c->seenShardT = 0;
-        void* bufs[] = {c->vk, c->vp, c->tq, c->pos, c->nrm, c->col, c->tris};
-        for (void* b : bufs)
-            if (b) (void)hipFree(b);
-        c->vk = nullptr; c->vp = nullptr; c->tq = nullptr; c->pos = nullptr; c->nrm = nullptr; c->col = nullptr; c->tris = nullptr;
-        c->capVk = c->capVp = c->capTq = c->capV = c->capT = 0;
+        c->vk.release();
+        c->vp.release();
+        c->tq.release();
+        c->pos.release();
+        c->nrm.release();
+        c->col.release();
+        c->tris.release();
         c->vcap = (uint32_t)value;
         c->tcap = (uint32_t)std::min<int64_t>(2 * value, 0xffffffffll);
         c->vShardCap = (uint32_t)std::max<int64_t>(16, value / kShards);
@@ -1146,8 +1133,7 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
     else if (option == PSGPU_OPT_SPANS && value >= 0 && value <= (1 << 20)) {
         // the next `value` runs record their kernel spans, one slot each (then none)
         if (c->pending) (void)hipStreamSynchronize(c->runStream);
-        if (c->spans) (void)hipFree(c->spans);
-        c->spans = nullptr;
+        c->spans.release();
         c->spanCap = c->spanNext = 0;
         drop_graphs(c);
         if (value > 0) {
@@ -1156,20 +1142,19 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
                 init[i] = ~0ull;
                 init[i + 1] = 0ull;
             }
-            PSGPU_CHECK(hipMalloc(&c->spans, init.size() * 8));
+            PSGPU_CHECK(c->spans.reserve(init.size(), Growth::Exact));
             PSGPU_CHECK(hipMemcpy(c->spans, init.data(), init.size() * 8, hipMemcpyHostToDevice));
             c->spanCap = (uint32_t)value;
         }
     }
     else if (option == PSGPU_OPT_STAMPS && value >= 0 && value <= (1 << 24)) {
         if (c->pending) (void)hipStreamSynchronize(c->runStream);
-        if (c->stamps) (void)hipFree(c->stamps);
-        c->stamps = nullptr;
+        c->stamps.release();
         c->stampCap = 0;
         drop_graphs(c);
         if (value > 0) {
             const size_t bytes = (size_t)kNumStampKernels * value * 24 + (size_t)value * 64;
-            PSGPU_CHECK(hipMalloc(&c->stamps, bytes));
+            PSGPU_CHECK(c->stamps.reserve(bytes / 8, Growth::Exact));  // whole 8-byte words
             PSGPU_CHECK(hipMemset(c->stamps, 0, bytes));  // a kernel a run does not launch leaves no rows
             c->stampCap = (uint32_t)value;
         }
@@ -1438,7 +1423,7 @@ int psgpu_live_bricks(psgpu_ctx* c, uint32_t* bricks, uint32_t capacity, uint32_
     const uint32_t n = c->hostCtr->liveBricks;
     *count = n;
     if (!bricks || n == 0) return PSGPU_RET_SUCCESS;
-    if (n > capacity || n > c->capLive) return PSGPU_RET_PARAM_ERROR;
+    if (n > capacity || n > c->liveList.cap) return PSGPU_RET_PARAM_ERROR;
     rc = set_device(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     std::vector<uint64_t> raw(n);
@@ -1587,11 +1572,10 @@ int psgpu_download_process_stats(psgpu_ctx* c, PsMpuProcessStats* out) {
     int khz = 0;
     PSGPU_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
     if (khz <= 0) return PSGPU_RET_DEVICE_ERROR;
-    if (!c->clockProbe)
-        PSGPU_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->clockProbe), 64,
-                                  hipHostMallocMapped | hipHostMallocCoherent));
+    PSGPU_CHECK(c->clockProbe.reserve(8, hipHostMallocMapped | hipHostMallocCoherent));
+    uint64_t* const probe = c->clockProbe;
     uint64_t* dProbe = nullptr;
-    PSGPU_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dProbe), c->clockProbe, 0));
+    PSGPU_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dProbe), probe, 0));
     auto host_ns = [] {
         timespec ts;
         clock_gettime(CLOCK_REALTIME, &ts);
@@ -1600,13 +1584,13 @@ int psgpu_download_process_stats(psgpu_ctx* c, PsMpuProcessStats* out) {
     int64_t bestWidth = INT64_MAX, hostMid = 0;
     uint64_t devAt = 0;
     for (int k = 0; k < 8; ++k) {
-        __atomic_store_n(c->clockProbe, 0ull, __ATOMIC_RELEASE);
+        __atomic_store_n(probe, 0ull, __ATOMIC_RELEASE);
         const int64_t h0 = host_ns();
         PSGPU_CHECK(launch_clock_probe(dProbe, c->stream));
         uint64_t d = 0;
-        for (uint64_t spin = 0; (d = __atomic_load_n(c->clockProbe, __ATOMIC_ACQUIRE)) == 0ull; ++spin)
+        for (uint64_t spin = 0; (d = __atomic_load_n(probe, __ATOMIC_ACQUIRE)) == 0ull; ++spin)
             if ((spin & 1023) == 1023 && hipStreamQuery(c->stream) != hipErrorNotReady) {
-                d = __atomic_load_n(c->clockProbe, __ATOMIC_ACQUIRE);
+                d = __atomic_load_n(probe, __ATOMIC_ACQUIRE);
                 if (d == 0ull) return PSGPU_RET_DEVICE_ERROR;  // finished (or failed) without a reading
                 break;
             }
@@ -1699,19 +1683,13 @@ int export_stage(psgpu_ctx* c, bool mesh, bool stats, ExportStage* st, hipEvent_
     // the packed mesh: pack_words per piece; bounded by 4 extra words per piece
     S.meshBytes = mesh ? 4 * (pack_words(V, T) + 4 * kExportPieces) : 0;
     const size_t total = up(S.oMesh + S.meshBytes);
-    if (total > c->hostStageCap) {
-        if (c->hostStage) (void)hipHostFree(c->hostStage);
-        c->hostStage = nullptr;
-        c->hostStageCap = 0;
-        const size_t cap = total + total / 4;
+    if (total > c->hostStage.cap) {
         // coherent: the export kernels write it directly over PCIe
-        PSGPU_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->hostStage), cap,
-                                  hipHostMallocMapped | hipHostMallocCoherent));
-        c->hostStageCap = cap;
-        memset(c->hostStage, 0, cap);  // no stale flag can equal an epoch
+        PSGPU_CHECK(c->hostStage.reserve(total + total / 4, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(c->hostStage, 0, c->hostStage.cap);  // no stale flag can equal an epoch
     }
     if (++c->exportEpoch == 0) {  // wrapped: clear every old flag
-        memset(c->hostStage, 0, c->hostStageCap);
+        memset(c->hostStage, 0, c->hostStage.cap);
         c->exportEpoch = 1;
     }
     S.epoch = c->exportEpoch;
@@ -1719,7 +1697,7 @@ int export_stage(psgpu_ctx* c, bool mesh, bool stats, ExportStage* st, hipEvent_
     if (c->debug & (1 << 23)) {  // test hook: every word past the flags reads as this call's epoch
         // (the stream is idle: the previous export's scatter synchronised with it)
         uint32_t* w = reinterpret_cast<uint32_t*>(h + flagBytes);
-        for (size_t i = 0, n = (c->hostStageCap - flagBytes) / 4; i < n; ++i) w[i] = S.epoch;
+        for (size_t i = 0, n = (c->hostStage.cap - flagBytes) / 4; i < n; ++i) w[i] = S.epoch;
     }
     hipStream_t s = c->stream;
     for (hipEvent_t& e : c->exportEv)
@@ -2030,10 +2008,11 @@ int psgpu_field_values(psgpu_ctx* c, const float* xyz, uint32_t n, int mode, flo
     if (rc != PSGPU_RET_SUCCESS) return rc;
     jit_poll(c, false);
     if (n == 0) return PSGPU_RET_SUCCESS;
-    float *dx = nullptr, *dout = nullptr, *dcol = nullptr;
-    PSGPU_CHECK(hipMalloc(&dx, (size_t)n * 12));
-    PSGPU_CHECK(hipMalloc(&dout, (size_t)n * 4));
-    PSGPU_CHECK(hipMalloc(&dcol, (size_t)n * 12));
+    DevBuf<float> bx, bout, bcol;  // freed on every return
+    PSGPU_CHECK(bx.reserve((size_t)n * 3, Growth::Exact));
+    PSGPU_CHECK(bout.reserve((size_t)n, Growth::Exact));
+    PSGPU_CHECK(bcol.reserve((size_t)n * 3, Growth::Exact));
+    float *dx = bx, *dout = bout, *dcol = bcol;
     PSGPU_CHECK(hipMemcpy(dx, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
     Params p = make_params(c, plan_run(c, false));
     hipError_t e;
@@ -2046,9 +2025,6 @@ int psgpu_field_values(psgpu_ctx* c, const float* xyz, uint32_t n, int mode, flo
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && colOut) e = hipMemcpy(colOut, dcol, (size_t)n * 12, hipMemcpyDeviceToHost);
-    (void)hipFree(dx);
-    (void)hipFree(dout);
-    (void)hipFree(dcol);
     return hip_fail(e, "psgpu_field_values");
 }
 

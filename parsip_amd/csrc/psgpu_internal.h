@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/parsip_gpu.h"
+#include "psgpu_buf.h"
 #include "psgpu_jit.h"
 #include "psgpu_model.h"
 #include "psgpu_plan.h"
@@ -35,15 +36,14 @@ constexpr int kWeldPhases = 6;  // psgpu_weld_times: the whole weld, then its fi
 // its buffers come with the first psgpu_weld_shells, grow on demand and go with the weld's.
 constexpr int kShellsPhases = 11;  // psgpu_weld_shells_times: the whole call, then its ten steps
 struct ShellsState {
-    unsigned char* table = nullptr;  // open-addressing edge table: keys (8 B a slot), then use counts (8 B a slot)
-    uint32_t* parent = nullptr;      // per welded vertex: union-find parent, then the shell index of a root
-    uint32_t* vertexShell = nullptr; // per welded vertex: its root, then its shell index
-    uint32_t* triShell = nullptr;    // per triangle
-    uint64_t* blockCnt = nullptr;    // per block of vertices: roots, scanned
-    unsigned char* ctl = nullptr;    // error word, largest |coordinate|, the mesh totals
-    unsigned char* acc = nullptr;    // per shell: counts, bounding box keys, the four integer sums
-    PsShell* shells = nullptr;
-    size_t capTable = 0, capV = 0, capT = 0, capBlocks = 0, capCtl = 0, capAcc = 0, capShells = 0;
+    DevBuf<unsigned char> table;   // open-addressing edge table: keys (8 B a slot), then use counts (8 B a slot)
+    DevBuf<uint32_t> parent;       // per welded vertex: union-find parent, then the shell index of a root
+    DevBuf<uint32_t> vertexShell;  // per welded vertex: its root, then its shell index
+    DevBuf<uint32_t> triShell;     // per triangle
+    DevBuf<uint64_t> blockCnt;     // per block of vertices: roots, scanned
+    DevBuf<unsigned char> ctl;     // error word, largest |coordinate|, the mesh totals
+    DevBuf<unsigned char> acc;     // per shell: counts, bounding box keys, the four integer sums
+    DevBuf<PsShell> shells;
     bool valid = false;              // holds the shells of the weld beside it (a new weld clears it)
     PsShellsInfo info{};
     hipEvent_t ev[kShellsPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: before the first step, after each
@@ -51,34 +51,21 @@ struct ShellsState {
 };
 
 struct WeldState {
-    unsigned char* table = nullptr;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
-    uint32_t* rep = nullptr;         // per input vertex: its representative (the smallest index on its edge)
-    uint32_t* kid = nullptr;         // per kept input vertex: its welded id
-    uint32_t* map = nullptr;         // vertexMap
-    uint64_t* blockCnt = nullptr;    // per block of vertices: kept | seam << 32, scanned
-    float* pos = nullptr;            // the welded mesh
-    float* nrm = nullptr;
-    float* col = nullptr;
-    uint32_t* tris = nullptr;
-    size_t capTable = 0, capV = 0, capBlocks = 0, capV3 = 0, capT3 = 0;
+    DevBuf<unsigned char> table;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
+    DevBuf<uint32_t> rep;         // per input vertex: its representative (the smallest index on its edge)
+    DevBuf<uint32_t> kid;         // per kept input vertex: its welded id
+    DevBuf<uint32_t> map;         // vertexMap
+    DevBuf<uint64_t> blockCnt;    // per block of vertices: kept | seam << 32, scanned
+    DevBuf<float> pos;            // the welded mesh
+    DevBuf<float> nrm;
+    DevBuf<float> col;
+    DevBuf<uint32_t> tris;
     uint64_t doneSeq = ~0ull;        // psgpu_ctx::runSeq of the run the buffers hold the weld of
     PsWeldInfo info{};
     hipEvent_t ev[kWeldPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: around the launches
     float lastMs[kWeldPhases] = {};
     ShellsState shells;               // psgpu_weld_shells of this weld
 };
-
-// Grow a device buffer to `need` elements (by half again at least); its contents are lost.
-template <typename T>
-hipError_t weld_grow(T*& ptr, size_t& cap, size_t need) {
-    if (need <= cap && ptr) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    const size_t n = std::max<size_t>(need, cap + cap / 2);
-    const hipError_t e = hipMalloc(&ptr, std::max<size_t>(n, 1) * sizeof(T));
-    cap = e == hipSuccess ? n : 0;
-    return e;
-}
 
 }  // namespace psgpu
 
@@ -100,8 +87,8 @@ struct psgpu_ctx {
     hipStream_t stream = nullptr;
     PsSoaBlobPrims primsHost;  // bbox + counts of the current model
     DevModel model{};
-    DevModel* dModel = nullptr;
-    CubeTablesDev* dTables = nullptr;
+    psgpu::DevBuf<DevModel> dModel;
+    psgpu::DevBuf<CubeTablesDev> dTables;
     int useJit = 1;
     int jitAsync = 1;                  // set_model returns while hiprtc compiles (interpreter meanwhile)
     std::shared_ptr<JitKernels> jit;   // specialised kernels of the current model
@@ -130,8 +117,7 @@ struct psgpu_ctx {
     psgpu::LastRun last;       // ... and the last finished run's counts
     psgpu::LaunchPlan run{};   // the launch shape of the last enqueued run
     bool splittable = false;  // the model's walk splits at the root (jit_splittable)
-    uint32_t* fqReady = nullptr;  // k_front: per queue entry, the tag of the run that published it
-    size_t capFq = 0;
+    psgpu::DevBuf<uint32_t> fqReady;  // k_front: per queue entry, the tag of the run that published it
     int timing = 0;
     // geometry of the last run
     float cs = 0.0f;
@@ -141,50 +127,43 @@ struct psgpu_ctx {
     bool pending = false;
     bool haveResult = false;
     // device buffers
-    size_t capLb = 0, capList = 0, capCounts = 0, capOff = 0, capVk = 0, capVp = 0, capTq = 0, capV = 0, capT = 0;
-    uint32_t* pq = nullptr;         // sharded S1 survivor queues
-    uint64_t* pqMask = nullptr;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
-    size_t capPqMask = 0;
-    uint64_t* liveList = nullptr;   // k_sieve's list of live bricks (one word per brick of the range)
-    size_t capLive = 0;
+    psgpu::DevBuf<uint32_t> pq;         // sharded S1 survivor queues
+    psgpu::DevBuf<uint64_t> pqMask;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
+    psgpu::DevBuf<uint64_t> liveList;   // k_sieve's list of live bricks (one word per brick of the range)
     uint32_t pShardCap = 0;
     float lastCs = 0.0f;            // the cell size of the last enqueued run
-    uint64_t* scanStatus = nullptr; // 2 x kScanMaxBlocks look-back words (alternating runs)
+    psgpu::DevBuf<uint64_t> scanStatus; // 2 x kScanMaxBlocks look-back words (alternating runs)
     uint32_t parity = 0;            // which counter / status set the next run uses
     // runs launched since the counter sets last started at epoch 0 = the next run's epoch
     // (DevCounters::epoch; k_front tags its queue entries epoch + 1, which must never wrap to 0)
     uint64_t epochRuns = 0;
-    uint64_t* counts = nullptr;
-    uint8_t* passed = nullptr;      // per MPU: passed S1
-    size_t capPassed = 0;
+    psgpu::DevBuf<uint64_t> counts;
+    psgpu::DevBuf<uint8_t> passed;      // per MPU: passed S1
     int bound = 1;                  // prove S1 survivors empty by field bounds in k_precheck
-    uint64_t* mpuMasks = nullptr;   // 4 words per MPU of the range (the same two masks, box + delta)
+    psgpu::DevBuf<uint64_t> mpuMasks;   // 4 words per MPU of the range (the same two masks, box + delta)
     bool opInside = true;           // PSGPU_OPT_OP_INSIDE: k_precheck makes op-inside masks
-    size_t capMasks = 0;
-    uint64_t* offs = nullptr;
-    VertexKey* vk = nullptr;
-    VertexPos* vp = nullptr;
-    TriRec* tq = nullptr;
-    float* pos = nullptr;
-    float* nrm = nullptr;
-    float* col = nullptr;
-    uint32_t* tris = nullptr;
-    DevCounters* ctr = nullptr;         // two sets, alternating runs
-    uint32_t* totals = nullptr;         // 8 words of the last run's totals (k_finish), for RCCL,
+    psgpu::DevBuf<uint64_t> offs;
+    psgpu::DevBuf<VertexKey> vk;
+    psgpu::DevBuf<VertexPos> vp;
+    psgpu::DevBuf<TriRec> tq;
+    psgpu::DevBuf<float> pos;
+    psgpu::DevBuf<float> nrm;
+    psgpu::DevBuf<float> col;
+    psgpu::DevBuf<uint32_t> tris;
+    psgpu::DevBuf<DevCounters> ctr;     // two sets, alternating runs
+    psgpu::DevBuf<uint32_t> totals;     // 8 words of the last run's totals (k_finish), for RCCL,
     uint32_t* emptyTotals = nullptr;    // then 8 words of an empty run's (totals + 8)
-    uint64_t* stamps = nullptr;         // per-wave timeline (PSGPU_OPT_STAMPS), 4 x stampCap x 3 words
+    psgpu::DevBuf<uint64_t> stamps;     // per-wave timeline (PSGPU_OPT_STAMPS), 4 x stampCap x 3 words
     uint32_t stampCap = 0;
-    uint64_t* spans = nullptr;          // per-run kernel spans (PSGPU_OPT_SPANS): spanCap x 4 x 2 words
+    psgpu::DevBuf<uint64_t> spans;      // per-run kernel spans (PSGPU_OPT_SPANS): spanCap x 4 x 2 words
     uint32_t spanCap = 0, spanNext = 0;
     int mpuTicksOpt = 0;                // PSGPU_OPT_MPU_TICKS: runs record per-MPU ticks (MPUSTATS)
-    uint64_t* mpuTicks = nullptr;       // 4 words per MPU of the range (Params::mpuTicks)
-    size_t capTicks = 0;
+    psgpu::DevBuf<uint64_t> mpuTicks;   // 4 words per MPU of the range (Params::mpuTicks)
     bool runTicks = false;              // the last enqueued run recorded them
-    uint64_t* clockProbe = nullptr;     // pinned, mapped: one device clock reading (k_clock_probe)
-    DevCounters* hostCtr = nullptr;     // pinned, mapped: written by k_finish
+    psgpu::PinnedBuf<uint64_t> clockProbe;  // pinned, mapped: one device clock reading (k_clock_probe)
+    psgpu::PinnedBuf<DevCounters> hostCtr;  // pinned, mapped: written by k_finish
     DevCounters* hostCtrDev = nullptr;  // its device address
-    unsigned char* hostStage = nullptr;  // pinned staging for the blocking PolyMPUs export
-    size_t hostStageCap = 0;
+    psgpu::PinnedBuf<unsigned char> hostStage;  // pinned staging for the blocking PolyMPUs export
     hipEvent_t exportEv[2] = {};         // the export's metadata, then its packing kernel
     uint32_t exportEpoch = 0;            // the blocking export's flag value (k_export_pack), never 0
     std::unique_ptr<psgpu::ScatterPool> scatterPool;  // the export's scatter threads, made on first use
@@ -237,6 +216,10 @@ struct WeldGathered {
     uint32_t V, T;
 };
 int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals);
+// What psgpu_weld_device / psgpu_download_weld and the group's twins hand out of a finished weld
+// (the callers check that W holds one; for the download its device is current).
+int weld_device(const WeldState& W, PsWeldDevice* out);
+int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap);
 // k_weld_scan on its own: blockCnt[0 .. blocks) becomes its exclusive scan, blockCnt[blocks] the
 // total (both 32-bit halves of a word are scanned), enqueued on s.
 void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s);
@@ -248,7 +231,6 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info);
 int shells_device(const WeldState& W, PsShellsDevice* out);
 int shells_download(const WeldState& W, PsShell* shells, uint32_t capacity, uint32_t* vertexShell, uint32_t* triShell);
 int shells_times(const WeldState& W, float* ms, int maxPhases, const char** names);
-void shells_state_free(ShellsState& S);
 // The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.

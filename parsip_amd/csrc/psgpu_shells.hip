@@ -512,15 +512,6 @@ inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBl
 
 }  // namespace
 
-void shells_state_free(ShellsState& S) {
-    void* bufs[] = {S.table, S.parent, S.vertexShell, S.triShell, S.blockCnt, S.ctl, S.acc, S.shells};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (hipEvent_t e : S.ev)
-        if (e) (void)hipEventDestroy(e);
-    S = ShellsState{};
-}
-
 int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     ShellsState& S = W.shells;
     const uint32_t V = W.info.ctVertices, T = W.info.ctTriangles;
@@ -537,27 +528,27 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     while (slots < 6ull * T) slots <<= 1;
     if (slots > (1ull << 31)) return PSGPU_RET_PARAM_ERROR;
     const uint32_t blocks = blocks_of(V);
-    size_t capParent = S.capV;
-    PSGPU_CHECK(weld_grow(S.table, S.capTable, (size_t)slots * 16));
-    PSGPU_CHECK(weld_grow(S.vertexShell, S.capV, (size_t)V));
-    PSGPU_CHECK(weld_grow(S.parent, capParent, (size_t)V));
-    PSGPU_CHECK(weld_grow(S.triShell, S.capT, (size_t)T));
-    PSGPU_CHECK(weld_grow(S.blockCnt, S.capBlocks, (size_t)blocks + 1));
-    PSGPU_CHECK(weld_grow(S.ctl, S.capCtl, sizeof(ShellsCtl)));
+    constexpr Growth H = Growth::ByHalf;
+    PSGPU_CHECK(S.table.reserve((size_t)slots * 16, H));
+    PSGPU_CHECK(S.vertexShell.reserve((size_t)V, H));
+    PSGPU_CHECK(S.parent.reserve((size_t)V, H));
+    PSGPU_CHECK(S.triShell.reserve((size_t)T, H));
+    PSGPU_CHECK(S.blockCnt.reserve((size_t)blocks + 1, H));
+    PSGPU_CHECK(S.ctl.reserve(sizeof(ShellsCtl), H));
     ShellsParams q;
     memset(&q, 0, sizeof(q));
     q.pos = W.pos;
     q.tris = W.tris;
     q.V = V;
     q.T = T;
-    q.keys = reinterpret_cast<uint64_t*>(S.table);
+    q.keys = reinterpret_cast<uint64_t*>(S.table.ptr);
     q.uses = reinterpret_cast<unsigned long long*>(S.table + (size_t)slots * 8);
     q.tableMask = (uint32_t)(slots - 1);
     q.parent = S.parent;
     q.vertexShell = S.vertexShell;
     q.triShell = S.triShell;
     q.blockCnt = S.blockCnt;
-    q.ctl = reinterpret_cast<ShellsCtl*>(S.ctl);
+    q.ctl = reinterpret_cast<ShellsCtl*>(S.ctl.ptr);
     if (timed)
         for (hipEvent_t& e : S.ev)
             if (!e) PSGPU_CHECK(hipEventCreate(&e));
@@ -596,9 +587,9 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     q.eA = 58 - 2 * k - L;
     q.eV = 58 - 3 * k - L;
     q.S = ctShells;
-    PSGPU_CHECK(weld_grow(S.acc, S.capAcc, (size_t)ctShells * sizeof(ShellAcc)));
-    PSGPU_CHECK(weld_grow(S.shells, S.capShells, (size_t)ctShells));
-    q.acc = reinterpret_cast<ShellAcc*>(S.acc);
+    PSGPU_CHECK(S.acc.reserve((size_t)ctShells * sizeof(ShellAcc), H));
+    PSGPU_CHECK(S.shells.reserve((size_t)ctShells, H));
+    q.acc = reinterpret_cast<ShellAcc*>(S.acc.ptr);
     q.shells = S.shells;
     hipLaunchKernelGGL(k_shells_ids, dim3(blocks), blk, 0, s, q);
     PSGPU_CHECK(mark());
@@ -646,9 +637,9 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
 int shells_device(const WeldState& W, PsShellsDevice* out) {
     if (!out || !W.shells.valid) return PSGPU_RET_PARAM_ERROR;
     const bool any = W.shells.info.ctShells != 0;  // an empty weld has no arrays
-    out->shells = any ? W.shells.shells : nullptr;
-    out->vertexShell = any ? W.shells.vertexShell : nullptr;
-    out->triShell = any ? W.shells.triShell : nullptr;
+    out->shells = any ? W.shells.shells.ptr : nullptr;
+    out->vertexShell = any ? W.shells.vertexShell.ptr : nullptr;
+    out->triShell = any ? W.shells.triShell.ptr : nullptr;
     return PSGPU_RET_SUCCESS;
 }
 

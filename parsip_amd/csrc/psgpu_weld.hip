@@ -374,19 +374,19 @@ int weld_prepare(WeldState& W, uint32_t V, uint32_t T, WeldParams& q, uint32_t* 
     uint32_t slots = 1024;
     while (slots < 2ull * V && slots < (1u << 31)) slots <<= 1;
     const uint32_t blocks = (V + kWeldBlock - 1) / kWeldBlock;
-    size_t capV3n = W.capV3, capV3c = W.capV3, capVk = W.capV, capVm = W.capV;
-    PSGPU_CHECK(weld_grow(W.table, W.capTable, (size_t)slots * 12));
-    PSGPU_CHECK(weld_grow(W.rep, W.capV, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.kid, capVk, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.map, capVm, (size_t)V + 4));
-    PSGPU_CHECK(weld_grow(W.blockCnt, W.capBlocks, (size_t)blocks + 1));
-    PSGPU_CHECK(weld_grow(W.pos, W.capV3, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.nrm, capV3n, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.col, capV3c, (size_t)V * 3));
-    PSGPU_CHECK(weld_grow(W.tris, W.capT3, (size_t)T * 3 + 4));
+    constexpr Growth H = Growth::ByHalf;
+    PSGPU_CHECK(W.table.reserve((size_t)slots * 12, H));
+    PSGPU_CHECK(W.rep.reserve((size_t)V + 4, H));
+    PSGPU_CHECK(W.kid.reserve((size_t)V + 4, H));
+    PSGPU_CHECK(W.map.reserve((size_t)V + 4, H));
+    PSGPU_CHECK(W.blockCnt.reserve((size_t)blocks + 1, H));
+    PSGPU_CHECK(W.pos.reserve((size_t)V * 3, H));
+    PSGPU_CHECK(W.nrm.reserve((size_t)V * 3, H));
+    PSGPU_CHECK(W.col.reserve((size_t)V * 3, H));
+    PSGPU_CHECK(W.tris.reserve((size_t)T * 3 + 4, H));
     q.V = V;
     q.T = T;
-    q.keys = reinterpret_cast<uint64_t*>(W.table);
+    q.keys = reinterpret_cast<uint64_t*>(W.table.ptr);
     q.mins = reinterpret_cast<uint32_t*>(W.table + (size_t)slots * 8);
     q.tableMask = slots - 1u;
     q.rep = W.rep;
@@ -427,13 +427,11 @@ bool weld_run_ready(const psgpu_ctx* c) {
 }
 
 void weld_state_free(WeldState& W) {
-    shells_state_free(W.shells);
-    void* bufs[] = {W.table, W.rep, W.kid, W.map, W.blockCnt, W.pos, W.nrm, W.col, W.tris};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
+    for (hipEvent_t e : W.shells.ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : W.ev)
         if (e) (void)hipEventDestroy(e);
-    W = WeldState{};
+    W = WeldState{};  // releases the weld's buffers and the shells'
 }
 
 void weld_free(psgpu_ctx* c) { weld_state_free(c->weld); }
@@ -464,6 +462,25 @@ int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s) {
     PSGPU_CHECK(hipMemsetAsync(edge, 0xff, (size_t)V * 8, s));
     hipLaunchKernelGGL(k_weld_edges, dim3((V + kWeldBlock - 1) / kWeldBlock), dim3(kWeldBlock), 0, s, q);
     PSGPU_CHECK(hipGetLastError());
+    return PSGPU_RET_SUCCESS;
+}
+
+int weld_device(const WeldState& W, PsWeldDevice* out) {
+    out->pos = W.pos;
+    out->nrm = W.nrm;
+    out->col = W.col;
+    out->tris = W.tris;
+    out->vertexMap = W.map;
+    return PSGPU_RET_SUCCESS;
+}
+
+int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap) {
+    const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
+    if (pos && V) PSGPU_CHECK(hipMemcpy(pos, W.pos, V * 12, hipMemcpyDeviceToHost));
+    if (nrm && V) PSGPU_CHECK(hipMemcpy(nrm, W.nrm, V * 12, hipMemcpyDeviceToHost));
+    if (col && V) PSGPU_CHECK(hipMemcpy(col, W.col, V * 12, hipMemcpyDeviceToHost));
+    if (tris && T) PSGPU_CHECK(hipMemcpy(tris, W.tris, T * 12, hipMemcpyDeviceToHost));
+    if (vertexMap && Vin) PSGPU_CHECK(hipMemcpy(vertexMap, W.map, Vin * 4, hipMemcpyDeviceToHost));
     return PSGPU_RET_SUCCESS;
 }
 
@@ -557,27 +574,14 @@ int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
 
 int psgpu_weld_device(psgpu_ctx* c, PsWeldDevice* out) {
     if (!out || !weld_run_ready(c) || c->weld.doneSeq != c->runSeq) return PSGPU_RET_PARAM_ERROR;
-    const WeldState& W = c->weld;
-    out->pos = W.pos;
-    out->nrm = W.nrm;
-    out->col = W.col;
-    out->tris = W.tris;
-    out->vertexMap = W.map;
-    return PSGPU_RET_SUCCESS;
+    return weld_device(c->weld, out);
 }
 
 int psgpu_download_weld(psgpu_ctx* c, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap) {
     if (!weld_run_ready(c) || c->weld.doneSeq != c->runSeq) return PSGPU_RET_PARAM_ERROR;
     const int rc = set_device(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
-    const WeldState& W = c->weld;
-    const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
-    if (pos && V) PSGPU_CHECK(hipMemcpy(pos, W.pos, V * 12, hipMemcpyDeviceToHost));
-    if (nrm && V) PSGPU_CHECK(hipMemcpy(nrm, W.nrm, V * 12, hipMemcpyDeviceToHost));
-    if (col && V) PSGPU_CHECK(hipMemcpy(col, W.col, V * 12, hipMemcpyDeviceToHost));
-    if (tris && T) PSGPU_CHECK(hipMemcpy(tris, W.tris, T * 12, hipMemcpyDeviceToHost));
-    if (vertexMap && Vin) PSGPU_CHECK(hipMemcpy(vertexMap, W.map, Vin * 4, hipMemcpyDeviceToHost));
-    return PSGPU_RET_SUCCESS;
+    return weld_download(c->weld, pos, nrm, col, tris, vertexMap);
 }
 
 int psgpu_weld_times(psgpu_ctx* c, float* ms, int maxPhases, const char** names) {

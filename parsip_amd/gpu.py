@@ -99,7 +99,7 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
-    "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks",
+    "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks", "psgpu_debug_device_bytes",
     "psgpu_group_weld", "psgpu_group_weld_device", "psgpu_group_download_weld", "psgpu_group_weld_times",
     "psgpu_weld_shells", "psgpu_weld_shells_device", "psgpu_download_weld_shells", "psgpu_weld_shells_times",
     "psgpu_group_weld_shells", "psgpu_group_weld_shells_device", "psgpu_group_download_weld_shells",
@@ -297,6 +297,13 @@ def model_image(model) -> bytes:
 
 def device_count() -> int:
     return int(load().psgpu_device_count())
+
+
+def device_bytes() -> int:
+    """Device memory the library holds now, in bytes, over every context of the process."""
+    fn = load().psgpu_debug_device_bytes  # bound here: PSGPU_AB_LIB may name a library from before it
+    fn.argtypes, fn.restype = [], ctypes.c_uint64
+    return int(fn())
 
 
 def split_costs(costs: np.ndarray, parts: int, begin: int = 0) -> np.ndarray:
