@@ -347,9 +347,10 @@ __device__ __forceinline__ bool op_colour_weights(uint32_t type, float lf, float
 // is not evaluated.  Every cullable primitive has a skeleton segment (CullSeg) whose
 // distance minus a radius bounds its distance from below and is 1-Lipschitz: Point
 // (a point), infinite Line (an unbounded segment), capped Cylinder with |axis| = 1
-// (its axis segment, radius r), axis-aligned Cube (its centre, radius s*sqrt(3)).  For
-// the wave's AABB with centre c and half-diagonal h every point q then has
-// d(q) >= d(c) - h.  The host marks a prim cullable only without a matrix and with
+// (its axis segment, radius r), axis-aligned Cube (its centre, radius s*sqrt(3); and
+// the cube itself, as a box).  For the wave's AABB with centre c and half-diagonal h every
+// point q then has d(q) >= d(c) - h, and the tighter bounds that treat the AABB as a box
+// and not as its sphere (cull_one, psgpu_model.h).  The host marks a prim cullable only without a matrix and with
 // finite, well-conditioned parameters; Cylinder also needs the AABB clear of its
 // infinite axis (where the reference's sqrt of a rounded-negative value is NaN).  The
 // margin d^2 >= 1.02 covers fp32 rounding of the reference formulas by orders of
@@ -381,7 +382,7 @@ __device__ __forceinline__ CullSeg load_cullseg(ModelPtr M, int i) {
     S.a[0] = f[0]; S.a[1] = f[1]; S.a[2] = f[2];
     S.u[0] = f[3]; S.u[1] = f[4]; S.u[2] = f[5];
     S.invUU = f[6]; S.radius = f[7];
-    S.tmin = f[8]; S.tmax = f[9]; S.axisClear = f[10]; S.pad = f[11];
+    S.tmin = f[8]; S.tmax = f[9]; S.axisClear = f[10]; S.boxHalf = f[11];
     return S;
 }
 
@@ -397,10 +398,10 @@ __device__ __forceinline__ CullLanes load_cull_lanes(ModelPtr M) {
 __device__ __forceinline__ CullMask cull_mask_from(const CullLanes& L, float x0, float y0, float z0, float x1,
                                                    float y1, float z1) {
     CullMask cm{0ull, 0ull};
-    float c[3], h;
-    if (!cull_box(x0, y0, z0, x1, y1, z1, c, &h)) return cm;
-    cm.lo = ballot(cull_one(L.s[0], c[0], c[1], c[2], h));
-    if (L.two) cm.hi = ballot(cull_one(L.s[1], c[0], c[1], c[2], h));
+    float c[3], h, he[3];
+    if (!cull_box(x0, y0, z0, x1, y1, z1, c, &h, he)) return cm;
+    cm.lo = ballot(cull_one(L.s[0], c[0], c[1], c[2], h, he));
+    if (L.two) cm.hi = ballot(cull_one(L.s[1], c[0], c[1], c[2], h, he));
     return cm;
 }
 
@@ -437,9 +438,10 @@ __device__ __forceinline__ bool culled(const CullMask& cm, uint32_t i) {
 // or lo >= 0.5 (no corner outside) gives exactly the reference result, 0 vertices and
 // 0 triangles.  The bound is conservative by construction:
 //  * each primitive's distance (Point, infinite Line, capped Cylinder, Cube: the same
-//    functions the reference evaluates, all true Euclidean distances, 1-Lipschitz) is
-//    evaluated at the box centre and widened by the half-diagonal h (+ 1e-4 and a
-//    relative 1e-4); Wyvill is monotone in the distance; the field interval is widened
+//    functions the reference evaluates, all true Euclidean distances to convex sets) is
+//    evaluated at the box centre and widened by what the box's half-extents allow towards
+//    and away from the primitive (prim_interval, psgpu_model.h: never more than the
+//    half-diagonal h); Wyvill is monotone in the distance; the field interval is widened
 //    by kBoundEps, orders of magnitude above the fp32 rounding of either evaluation;
 //  * ops are monotone interval maps (Blend, Union, Intersect, Dif, SmoothDif, warps);
 //  * op-box pruning (depth > 3) is decided per quad of 4 z-consecutive corners: from
@@ -449,56 +451,17 @@ __device__ __forceinline__ bool culled(const CullMask& cm, uint32_t i) {
 // matrix, and a type above (or Triangle, field 0) are bounded (DevModel::boundable, set
 // by the host; Ricci and unknown ops are excluded), so no corner can be NaN -- except a
 // Cylinder on its own axis, where the bound gives up (ok = false) within 0.05 of it.
-constexpr float kBoundEps = 2e-4f;
-
 struct BoundBox {
     float cx, cy, cz, h;       // centre, half-diagonal (with margin)
+    float hx, hy, hz;          // half-extents
     float xs[4], ys[4], zs[4]; // the box's corner coordinates per axis (z: one S2 quad)
 };
 
-template <int TYPE, class PR>
-__device__ __forceinline__ float prim_true_dist(PR& P, float x, float y, float z, float* axisD) {
-    float d2 = 0.0f;
-    if (TYPE == PSGPU_T_POINT) {
-        const float dx = x - P.pos[0], dy = y - P.pos[1], dz = z - P.pos[2];
-        d2 = dx * dx + dy * dy + dz * dz;
-    } else if (TYPE == PSGPU_T_LINE) {  // distance from the infinite line (the reference does not clamp)
-        const float ux = P.dir[0] - P.pos[0], uy = P.dir[1] - P.pos[1], uz = P.dir[2] - P.pos[2];
-        const float dx = x - P.pos[0], dy = y - P.pos[1], dz = z - P.pos[2];
-        const float t = (dx * ux + dy * uy + dz * uz) / (ux * ux + uy * uy + uz * uz);
-        const float ex = dx - t * ux, ey = dy - t * uy, ez = dz - t * uz;
-        d2 = ex * ex + ey * ey + ez * ez;
-    } else if (TYPE == PSGPU_T_CYLINDER) {  // solid cylinder: axis dir (unit), radius res0, height res1
-        const float px = x - P.pos[0], py = y - P.pos[1], pz = z - P.pos[2];
-        float yy = px * P.dir[0] + py * P.dir[1] + pz * P.dir[2];
-        const float rr = px * px + py * py + pz * pz - yy * yy;
-        const float r = __builtin_amdgcn_sqrtf(rr > 0.0f ? rr : 0.0f);
-        *axisD = r;
-        const float xx = fmaxf(r - P.res[0], 0.0f);
-        yy = yy > 0.0f ? fmaxf(yy - P.res[1], 0.0f) : yy;
-        d2 = xx * xx + yy * yy;
-    } else if (TYPE == PSGPU_T_CUBE) {
-        const float ex = fmaxf(fabsf(x - P.pos[0]) - P.res[0], 0.0f);
-        const float ey = fmaxf(fabsf(y - P.pos[1]) - P.res[0], 0.0f);
-        const float ez = fmaxf(fabsf(z - P.pos[2]) - P.res[0], 0.0f);
-        d2 = ex * ex + ey * ey + ez * ez;
-    }
-    return __builtin_amdgcn_sqrtf(d2);
-}
-
-__device__ __forceinline__ float wyvill_of_dist(float d) {
-    const float t = 1.0f - d * d;
-    return t > 0.0f ? (t * t) * t : 0.0f;
-}
-
-// Field interval of one primitive over the box (TYPE: Point, Line, Cylinder or Cube).
+// Field interval of one primitive over the box (TYPE: Point, Line, Cylinder or Cube): the
+// interval arithmetic is prim_interval's (psgpu_model.h, host and device).
 template <int TYPE, class PR>
 __device__ __forceinline__ void prim_bound(PR& P, const BoundBox& B, float* lo, float* hi, bool* ok) {
-    float axisD = 1e30f;
-    const float d = prim_true_dist<TYPE, PR>(P, B.cx, B.cy, B.cz, &axisD);
-    if (TYPE == PSGPU_T_CYLINDER) *ok = *ok && (axisD - B.h > 0.05f);
-    *hi = wyvill_of_dist(fmaxf(d - B.h, 0.0f)) + kBoundEps;
-    *lo = wyvill_of_dist(d + B.h) - kBoundEps;
+    prim_interval<TYPE, PR>(P, B.cx, B.cy, B.cz, B.h, B.hx, B.hy, B.hz, lo, hi, ok);
 }
 
 // Interval of a binary op (the monotone maps of op_field; Ricci/unknown types are not bounded).
@@ -789,7 +752,11 @@ __device__ __forceinline__ void stamp_live_word(const Params& p, bool on, const 
 // Field bounds (see prim_bound): lane c of an MPU bounds the 4x4x4 corners [4X, 4X+3] x
 // [4Y, 4Y+3] x [4Z, 4Z+3] of its S2 cache (its z range is exactly one S2 quad), at the S2
 // coordinates (block_s2_inside_bits): o + (float)index * cs.  The one definition of the
-// half-diagonal's slack.
+// half-diagonal's slack, and of the half-extents': one wave-uniform value for the three axes
+// and every octant of the lattice.  An octant's corners are fl(o + fl(k cs)), k = 4X .. 4X + 3,
+// each within 2^-24 (|x| + 7 cs) of o + k cs, so the box reaches at most 1.5 cs + 2^-24 M from
+// its true centre, M = the lattice's largest coordinate magnitude + 7 cs, and the centre as
+// computed is within 2^-24 M of the true one: 1.5 cs + 2.4e-7 M covers both twice.
 __device__ __forceinline__ BoundBox octant_box(const Params& p, const float o[3], int c) {
     BoundBox B;
 #pragma unroll
@@ -803,6 +770,11 @@ __device__ __forceinline__ BoundBox octant_box(const Params& p, const float o[3]
     B.cy = 0.5f * (B.ys[0] + B.ys[3]);
     B.cz = 0.5f * (B.zs[0] + B.zs[3]);
     B.h = __builtin_amdgcn_sqrtf(hx * hx + hy * hy + hz * hz) * 1.0001f + 1e-4f;
+    float mag = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        mag = fmaxf(mag, fmaxf(fabsf(p.lo[a]), fabsf(p.lo[a] + (float)p.dims[a] * p.side)));
+    B.hx = B.hy = B.hz = (1.5f * p.cs + 2.4e-7f * (mag + p.side)) * 1.0001f + 1e-4f;
     return B;
 }
 

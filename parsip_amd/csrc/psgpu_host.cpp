@@ -324,6 +324,7 @@ int build_device_model(const PsSoaBlobPrims& P, const PsSoaPrimMatrices& Mx, con
         cs.tmin = 0.0f;
         cs.tmax = 1.0f;
         cs.axisClear = -inf;
+        cs.boxHalf = inf;  // not an axis-aligned box: no gap form
         uint32_t flags = c ? 1u : 0u;
         if (c) {
             for (int a = 0; a < 3; ++a) cs.a[a] = d.pos[a];
@@ -341,6 +342,9 @@ int build_device_model(const PsSoaBlobPrims& P, const PsSoaPrimMatrices& Mx, con
                 flags |= 4u;
             } else if (d.type == PSGPU_PRIM_CUBE) {
                 cs.radius = (float)(d.res[0] * 1.7320508075688772 * (1.0 + 1e-6));
+                cs.boxHalf = d.res[0];
+            } else {
+                cs.boxHalf = 0.0f;  // Point
             }
             for (int a = 0; a < 3; ++a) uu += (double)cs.u[a] * cs.u[a];
             cs.invUU = uu > 0.0 ? (float)(1.0 / uu) : 0.0f;
@@ -351,7 +355,10 @@ int build_device_model(const PsSoaBlobPrims& P, const PsSoaPrimMatrices& Mx, con
         } else if (d.type == PSGPU_PRIM_TRIANGLE) {
             cs.radius = -inf;  // field exactly 0 everywhere (dist2 = FLT_MAX)
         }
-        if (i >= P.ctPrims) cs.radius = inf;  // (the culling masks only cover ctPrims)
+        if (i >= P.ctPrims) {  // (the culling masks only cover ctPrims)
+            cs.radius = inf;
+            cs.boxHalf = inf;
+        }
         d.cullable = flags;
     }
     // field bounds (k_precheck, prim_bound in psgpu_device.h) need every primitive the

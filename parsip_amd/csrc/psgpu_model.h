@@ -168,7 +168,9 @@ struct CullSeg {         // 48 B: three 16-B loads per lane
     float tmin, tmax;
     float axisClear;     // the box must keep this distance from the segment's line (Cylinder: its
                          // rounded-negative sqrt is NaN on the axis); -inf: no condition
-    float pad;
+    float boxHalf;       // the primitive is the axis-aligned box of this half side round A (Point: 0,
+                         // Cube: its half side), which the gap form of cull_one uses; +inf: it is not
+                         // one (Line, Cylinder, every slot that is never culled) and the form gives 0
 };
 static_assert(sizeof(CullSeg) == 48, "CullSeg size");
 
@@ -194,7 +196,32 @@ PSGPU_HDI bool cull_box(float x0, float y0, float z0, float x1, float y1, float 
     return true;
 }
 
-// Is the segment's primitive exactly +0 over the box (centre c, half-diagonal h)?
+// Half-extent of [x0, x1] about the centre c as computed (0.5f * (x0 + x1), rounded: off the true
+// centre by at most half an ulp of c, 2^-24 |c|, which the last term covers twice over).
+PSGPU_HDI float box_half_extent(float x0, float x1, float c) { return 0.5f * (x1 - x0) + __builtin_fabsf(1.2e-7f * c); }
+
+// The same, and the box's half-extents e along x, y, z, each grown by its rounding as h is.
+PSGPU_HDI bool cull_box(float x0, float y0, float z0, float x1, float y1, float z1, float c[3], float* h,
+                        float e[3]) {
+    if (!cull_box(x0, y0, z0, x1, y1, z1, c, h)) return false;
+    e[0] = box_half_extent(x0, x1, c[0]) * 1.0001f + 1e-6f;
+    e[1] = box_half_extent(y0, y1, c[1]) * 1.0001f + 1e-6f;
+    e[2] = box_half_extent(z0, z1, c[2]) * 1.0001f + 1e-6f;
+    return true;
+}
+
+// 1 / x for the box bounds: the device's v_rcp_f32 (1 ulp, inside the bounds' relative 1e-4)
+PSGPU_HDI float cull_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+
+// Is the segment's primitive exactly +0 over the box (centre c, half-diagonal h)?  The box as its
+// circumscribed sphere: the distance d to the skeleton is 1-Lipschitz, so d(q) >= d(c) - h at
+// every point q of the box.  (k_sieve's form, which tests/cpp/sieve_check.cpp compiles.)
 PSGPU_HDI bool cull_one(const CullSeg& S, float cx, float cy, float cz, float h) {
     const float dx = cx - S.a[0], dy = cy - S.a[1], dz = cz - S.a[2];
     const float t = (dx * S.u[0] + dy * S.u[1] + dz * S.u[2]) * S.invUU;
@@ -204,6 +231,124 @@ PSGPU_HDI bool cull_one(const CullSeg& S, float cx, float cy, float cz, float h)
     const float ex = dx - tc * S.u[0], ey = dy - tc * S.u[1], ez = dz - tc * S.u[2];
     const float d = (cull_sqrt(ex * ex + ey * ey + ez * ez) - S.radius) - h;
     return d > 0.0f && d * d >= 1.02f && (lineDist - h > S.axisClear);
+}
+
+// The same question with the box as the box it is (half-extents he, from cull_box).  A skeleton
+// K (a point, a line, a segment) is a convex set, and so is an axis-aligned cube.  Let p* be the
+// point of K nearest the box centre c and e = c - p*.  K lies in the half-space
+// <x - p*, e> <= 0 (the projection inequality), so for q = c + w in the box
+//   support form   d(q) >= <q - p*, e> / |e| = |e| + <w, e> / |e|
+//                       >= |e| - (he_x |e_x| + he_y |e_y| + he_z |e_z|) / |e|,
+// which by Cauchy-Schwarz is never below the sphere's |e| - h: a box whose face is turned
+// towards K pays its half-side, not its half-diagonal.  Where the primitive is itself an
+// axis-aligned box of half side s round A (Point: s = 0; Cube) the distance between the two
+// boxes is exact:
+//   gap form       d(q) >= sqrt(sum_a max(0, |c_a - A_a| - he_a - s)^2),
+// and it replaces the cube's ball of radius s sqrt(3).  The bound is the maximum of the three,
+// so it culls whatever the sphere form culls.  Every new term is rounded against culling (the
+// half-extents and the support term grow by a relative 1e-4 and 1e-6); |e| = 0 or a non-finite
+// term gives NaN or -inf, which the maximum drops.  The acceptance d > 0, d^2 >= 1.02 and the
+// axis clearance are the sphere form's.
+PSGPU_HDI bool cull_one(const CullSeg& S, float cx, float cy, float cz, float h, const float he[3]) {
+    const float dx = cx - S.a[0], dy = cy - S.a[1], dz = cz - S.a[2];
+    const float t = (dx * S.u[0] + dy * S.u[1] + dz * S.u[2]) * S.invUU;
+    const float lx = dx - t * S.u[0], ly = dy - t * S.u[1], lz = dz - t * S.u[2];
+    const float lineDist = cull_sqrt(lx * lx + ly * ly + lz * lz);
+    const float tc = __builtin_fminf(__builtin_fmaxf(t, S.tmin), S.tmax);
+    const float ex = dx - tc * S.u[0], ey = dy - tc * S.u[1], ez = dz - tc * S.u[2];
+    const float n = cull_sqrt(ex * ex + ey * ey + ez * ez);
+    const float sphere = (n - S.radius) - h;
+    const float reach = (he[0] * __builtin_fabsf(ex) + he[1] * __builtin_fabsf(ey) + he[2] * __builtin_fabsf(ez)) *
+                        cull_rcp(n);
+    const float support = (n - S.radius) - (reach * 1.0001f + 1e-6f);
+    const float gx = __builtin_fmaxf((__builtin_fabsf(dx) - he[0]) - S.boxHalf, 0.0f);
+    const float gy = __builtin_fmaxf((__builtin_fabsf(dy) - he[1]) - S.boxHalf, 0.0f);
+    const float gz = __builtin_fmaxf((__builtin_fabsf(dz) - he[2]) - S.boxHalf, 0.0f);
+    const float gap = cull_sqrt(gx * gx + gy * gy + gz * gz);
+    const float d = __builtin_fmaxf(__builtin_fmaxf(sphere, support), gap);  // fmaxf drops a NaN
+    return d > 0.0f && d * d >= 1.02f && (lineDist - h > S.axisClear);
+}
+
+// Field interval of one primitive over a box (the field bounds of k_precheck: see prim_bound,
+// psgpu_device.h, which explains what the interval proves).  Point, infinite Line, solid capped
+// Cylinder and axis-aligned Cube are convex sets K, and the functions below are their true
+// Euclidean distances.  With p* the point of K nearest the box centre c, e = c - p* and d = |e|,
+// every point q = c + w of the box (half-extents hx, hy, hz; half-diagonal h) has
+//   d(q) >= d - h                                        (1-Lipschitz)
+//   d(q) >= d - (hx |e_x| + hy |e_y| + hz |e_z|) / d     (support form, see cull_one; >= d - h)
+//   d(q) >= sqrt(sum_a max(0, |e_a| - h_a)^2)            (Point, Cube: the boxes' exact gap)
+//   d(q) <= |q - p*| <= sqrt(sum_a (|e_a| + h_a)^2)      (<= d + h by the triangle inequality)
+// and Wyvill's field is monotone in the distance.  h and the half-extents come with their slack
+// (octant_box: a relative 1e-4 and 1e-4, which every term above inherits), and the field
+// interval is widened by kBoundEps, orders of magnitude above the fp32 rounding of either
+// evaluation (where d > 2 that rounding may exceed the slack, and the field is 0 at either
+// end).  d = 0 makes the support term NaN, which fmaxf drops.
+constexpr float kBoundEps = 2e-4f;
+
+// Distance of (x, y, z) from the primitive; ev = |e_a|; axisD: a Cylinder's distance from its axis.
+template <int TYPE, class PR>
+PSGPU_HDI float prim_true_dist(PR& P, float x, float y, float z, float* axisD, float ev[3]) {
+    float d2 = 0.0f;
+    ev[0] = ev[1] = ev[2] = 0.0f;
+    if (TYPE == PSGPU_T_POINT) {
+        const float dx = x - P.pos[0], dy = y - P.pos[1], dz = z - P.pos[2];
+        ev[0] = __builtin_fabsf(dx); ev[1] = __builtin_fabsf(dy); ev[2] = __builtin_fabsf(dz);
+        d2 = dx * dx + dy * dy + dz * dz;
+    } else if (TYPE == PSGPU_T_LINE) {  // distance from the infinite line (the reference does not clamp)
+        const float ux = P.dir[0] - P.pos[0], uy = P.dir[1] - P.pos[1], uz = P.dir[2] - P.pos[2];
+        const float dx = x - P.pos[0], dy = y - P.pos[1], dz = z - P.pos[2];
+        const float t = (dx * ux + dy * uy + dz * uz) / (ux * ux + uy * uy + uz * uz);
+        const float ex = dx - t * ux, ey = dy - t * uy, ez = dz - t * uz;
+        ev[0] = __builtin_fabsf(ex); ev[1] = __builtin_fabsf(ey); ev[2] = __builtin_fabsf(ez);
+        d2 = ex * ex + ey * ey + ez * ez;
+    } else if (TYPE == PSGPU_T_CYLINDER) {  // solid cylinder: axis dir (unit), radius res0, height res1
+        const float px = x - P.pos[0], py = y - P.pos[1], pz = z - P.pos[2];
+        float yy = px * P.dir[0] + py * P.dir[1] + pz * P.dir[2];
+        const float rr = px * px + py * py + pz * pz - yy * yy;
+        const float r = cull_sqrt(rr > 0.0f ? rr : 0.0f);
+        *axisD = r;
+        const float xx = __builtin_fmaxf(r - P.res[0], 0.0f);
+        const float k = xx > 0.0f ? xx * cull_rcp(r) : 0.0f;  // e = its radial part + its axial part
+        const float ya = yy > 0.0f ? __builtin_fmaxf(yy - P.res[1], 0.0f) : yy;
+        ev[0] = __builtin_fabsf(k * (px - yy * P.dir[0]) + ya * P.dir[0]);
+        ev[1] = __builtin_fabsf(k * (py - yy * P.dir[1]) + ya * P.dir[1]);
+        ev[2] = __builtin_fabsf(k * (pz - yy * P.dir[2]) + ya * P.dir[2]);
+        d2 = xx * xx + ya * ya;
+    } else if (TYPE == PSGPU_T_CUBE) {
+        ev[0] = __builtin_fmaxf(__builtin_fabsf(x - P.pos[0]) - P.res[0], 0.0f);
+        ev[1] = __builtin_fmaxf(__builtin_fabsf(y - P.pos[1]) - P.res[0], 0.0f);
+        ev[2] = __builtin_fmaxf(__builtin_fabsf(z - P.pos[2]) - P.res[0], 0.0f);
+        d2 = ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2];
+    }
+    return cull_sqrt(d2);
+}
+
+PSGPU_HDI float wyvill_of_dist(float d) {
+    const float t = 1.0f - d * d;
+    return t > 0.0f ? (t * t) * t : 0.0f;
+}
+
+// Field interval of one primitive (TYPE: Point, Line, Cylinder or Cube) over the box with centre
+// c, half-diagonal h and half-extents hx, hy, hz (all with their slack).  A Cylinder within 0.05 of its
+// own axis (where the reference's sqrt of a rounded-negative value is NaN) clears *ok.
+template <int TYPE, class PR>
+PSGPU_HDI void prim_interval(PR& P, float cx, float cy, float cz, float h, float hx, float hy, float hz, float* lo,
+                             float* hi, bool* ok) {
+    float axisD = 1e30f, ev[3];
+    const float d = prim_true_dist<TYPE, PR>(P, cx, cy, cz, &axisD, ev);
+    if (TYPE == PSGPU_T_CYLINDER) *ok = *ok && (axisD - h > 0.05f);
+    const float reach = (hx * ev[0] + hy * ev[1] + hz * ev[2]) * cull_rcp(d);
+    float loD = __builtin_fmaxf(d - h, d - reach);
+    const float ux = ev[0] + hx, uy = ev[1] + hy, uz = ev[2] + hz;
+    const float hiD = __builtin_fminf(d + h, cull_sqrt(ux * ux + uy * uy + uz * uz));
+    if (TYPE == PSGPU_T_POINT || TYPE == PSGPU_T_CUBE) {
+        const float gx = __builtin_fmaxf(ev[0] - hx, 0.0f);
+        const float gy = __builtin_fmaxf(ev[1] - hy, 0.0f);
+        const float gz = __builtin_fmaxf(ev[2] - hz, 0.0f);
+        loD = __builtin_fmaxf(loD, cull_sqrt(gx * gx + gy * gy + gz * gz));
+    }
+    *hi = wyvill_of_dist(__builtin_fmaxf(loD, 0.0f)) + kBoundEps;
+    *lo = wyvill_of_dist(hiD) - kBoundEps;
 }
 
 // The S1 corner box of the 2x2x2 brick of MPUs (bi, bj, bk) (brick coordinates of the lattice),

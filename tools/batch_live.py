@@ -2,8 +2,8 @@
 
 A k_vertex / k_finish wave takes 64 consecutive records of one vertex shard queue and walks every
 primitive that is live for any of the MPUs those records belong to (cull_mask_mpus: the AND of
-the MPUs' culling masks).  This computes the per-MPU masks on the CPU with cull_one's formula
-(psgpu_device.h) on the MPU box grown by 7 cs + 0.001, as k_precheck makes them, takes a queue
+the MPUs' culling masks).  This computes the per-MPU masks on the CPU with cull_one's sphere form
+(psgpu_model.h; the kernels' box form culls a few per cent more: tools/cull_pairs.py) on the MPU box grown by 7 cs + 0.001, as k_precheck makes them, takes a queue
 layout -- simulated, or downloaded from the GPU with Polygonizer.vertex_queue() -- and reports
 the vertex-weighted mean and histogram of live primitives per batch.
 
