@@ -33,111 +33,6 @@ using namespace psgpu;
 namespace {
 
 // ---------------------------------------------------------------------------
-// Marching-cubes table.  Generated, not transcribed: Bloomenthal's cube-table
-// construction ("An Implicit Surface Polygonizer", Graphics Gems IV, 1994) walks
-// each sign-changing edge clockwise around the cube faces to build polygons; the
-// reference's g_triTableCache (_CellConfigTable.h:60-317) keeps polygons in
-// discovery order with each polygon's edges in reverse walk order and fans
-// triangles about the last edge.  Corner c: bit2 = x, bit1 = y, bit0 = z.
-struct CubeTables {
-    int8_t tri[256][16];
-    uint8_t ntri[256];
-    uint8_t corner1[12], corner2[12], axis[12];
-};
-
-const CubeTables& cube_tables() {
-    static CubeTables T;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        // edges LB LT LN LF RB RT RN RF BN BF TN TF; faces L R B T N F
-        static const uint8_t c1[12] = {0, 2, 0, 1, 4, 6, 4, 5, 0, 1, 2, 3};
-        static const uint8_t c2[12] = {1, 3, 2, 3, 5, 7, 6, 7, 4, 5, 6, 7};
-        static const uint8_t ax[12] = {2, 2, 1, 1, 2, 2, 1, 1, 0, 0, 0, 0};
-        static const uint8_t lface[12] = {2, 0, 0, 5, 1, 3, 4, 1, 4, 2, 3, 5};
-        static const uint8_t rface[12] = {0, 3, 4, 0, 2, 1, 1, 5, 2, 5, 4, 3};
-        // next clockwise edge around `face` after `edge`: {face of the edge's first
-        // listed face, next-if-that-face, next-otherwise}
-        static const uint8_t ccwFace[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3};
-        static const uint8_t nextOn[12] = {3, 2, 0, 1, 6, 7, 5, 4, 4, 0, 1, 5};
-        static const uint8_t nextOff[12] = {8, 11, 10, 9, 9, 10, 8, 11, 2, 7, 6, 3};
-        memcpy(T.corner1, c1, 12);
-        memcpy(T.corner2, c2, 12);
-        memcpy(T.axis, ax, 12);
-        for (int cfg = 0; cfg < 256; ++cfg) {
-            auto in = [cfg](int c) { return (cfg >> c) & 1; };
-            bool done[12] = {};
-            std::vector<int> rows;
-            for (int e = 0; e < 12; ++e) {
-                if (done[e] || in(c1[e]) == in(c2[e])) continue;
-                std::vector<int> poly;
-                int edge = e, face = in(c1[e]) ? rface[e] : lface[e];
-                for (;;) {
-                    edge = (face == ccwFace[edge]) ? nextOn[edge] : nextOff[edge];
-                    done[edge] = true;
-                    if (in(c1[edge]) != in(c2[edge])) {
-                        poly.insert(poly.begin(), edge);
-                        if (edge == e) break;
-                        face = (face == lface[edge]) ? rface[edge] : lface[edge];
-                    }
-                }
-                const int np = (int)poly.size();
-                for (int t = np - 3; t >= 0; --t) {
-                    rows.push_back(poly[t]);
-                    rows.push_back(poly[t + 1]);
-                    rows.push_back(poly[np - 1]);
-                }
-            }
-            for (int i = 0; i < 16; ++i) T.tri[cfg][i] = i < (int)rows.size() ? (int8_t)rows[i] : (int8_t)-1;
-            T.ntri[cfg] = (uint8_t)(rows.size() / 3);
-        }
-    });
-    return T;
-}
-
-// Packed device tables (psgpu_model.h CubeTablesDev).
-void fill_device_tables(const CubeTables& T, CubeTablesDev& D) {
-    memset(&D, 0, sizeof(D));
-    for (int c = 0; c < 256; ++c) {
-        uint64_t row = 0, order = 0;
-        uint32_t seen = 0;
-        int nd = 0;
-        for (int e = 0; e < 16 && T.tri[c][e] >= 0; ++e) {
-            const int ed = T.tri[c][e];
-            row |= (uint64_t)ed << (4 * e);
-            if (!((seen >> ed) & 1u)) {
-                seen |= 1u << ed;
-                order |= (uint64_t)ed << (4 * nd++);
-            }
-        }
-        uint32_t cross = 0;
-        for (int e = 0; e < 12; ++e)
-            if (((c >> T.corner1[e]) & 1) != ((c >> T.corner2[e]) & 1)) cross |= 1u << e;
-        D.row[c] = row;
-        D.order[c] = order;
-        D.cross[c] = (uint16_t)cross;
-        D.ntri[c] = T.ntri[c];
-        D.crossNtri[c] = cross | ((uint32_t)T.ntri[c] << 16);
-    }
-    // ownership: the first cell in (i,j,k) order containing an edge owns it; an edge
-    // starting at cell corner (cx,cy,cz) on axis a is owned by this cell iff every
-    // non-axis corner bit is 1 or the cell sits on that axis' low boundary
-    for (int b = 0; b < 8; ++b) {
-        const bool i0 = b & 4, j0 = b & 2, k0 = b & 1;
-        uint32_t m = 0;
-        for (int e = 0; e < 12; ++e) {
-            const int c1 = T.corner1[e], ax = T.axis[e];
-            const bool bx = (c1 >> 2) & 1, by = (c1 >> 1) & 1, bz = c1 & 1;
-            const bool okx = ax == 0 || bx || i0, oky = ax == 1 || by || j0, okz = ax == 2 || bz || k0;
-            if (okx && oky && okz) m |= 1u << e;
-        }
-        D.own[b] = (uint16_t)m;
-    }
-    uint64_t edge = 0;
-    for (int e = 0; e < 12; ++e) edge |= (uint64_t)(T.corner1[e] | (T.axis[e] << 3)) << (5 * e);
-    D.edge = edge;
-}
-
-// ---------------------------------------------------------------------------
 // Walk program: the reference's processing order of fieldValue's explicit stack.
 bool op_needs_left(int t) { return (t >= 14 && t <= 19) || (t >= 22 && t <= 25); }
 bool op_needs_right(int t) { return t >= 14 && t <= 19; }
