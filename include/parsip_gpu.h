@@ -358,6 +358,80 @@ int  psgpu_download_weld_shells(psgpu_ctx* ctx, PsShell* shells, uint32_t capaci
  * whole call (its two host reads included), then its ten steps; returns the count filled. */
 int  psgpu_weld_shells_times(psgpu_ctx* ctx, float* ms, int maxPhases, const char** names);
 
+/* ---- the welded mesh filtered by shell: keep, drop, compact -------------------------------
+ * Shell s of the current psgpu_weld_shells result is kept iff all of these hold:
+ *     mask == NULL || mask[s] != 0
+ *     ctVertices  >= minVertices
+ *     ctTriangles >= minTriangles
+ *     area >= minArea
+ *     fabs(volume) >= minAbsVolume
+ *     with PSGPU_FILTER_CLOSED_ONLY:   the shell is closed (above: it has triangles and no
+ *                                      open, flipped or non-manifold edge)
+ *     with PSGPU_FILTER_DROP_CAVITIES: not (the shell is closed and volume < 0)
+ * The comparisons are plain IEEE comparisons of the PsShell fields as stored, so the device and
+ * meshio.filter_shells (plain numpy) decide identically from identical bytes.
+ *
+ * The filtered mesh is the stable compaction of the welded mesh:
+ *   - kept vertices, in welded order, keep pos / nrm / col bit for bit;
+ *   - kept triangles, in order, become vertexMap[tris] (a kept triangle's corners are kept: a
+ *     triangle's shell is its vertices' shell);
+ *   - vertexMap[v] is the filtered id of welded vertex v, 0xffffffff if v is dropped;
+ *   - shellMap[s] is the new index of shell s, 0xffffffff if s is dropped;
+ *   - shells[] holds the kept shells' PsShell records in order, firstVertex remapped through
+ *     vertexMap and no other field changed.
+ * Stable compaction is monotone, so shell order is preserved: the kept shells' firstVertex
+ * values still increase.  Area and volume in shells[] are the values of the unfiltered call:
+ * the fixed-point scales eA / eV depend on M and T of the mesh that was measured, so a fresh
+ * meshio.shells of the filtered mesh equals the kept records in every integer field and
+ * bounding box, and in area and volume only up to the fixed-point resolution (each of the T
+ * terms is floored twice, to 2^-(e+30): below T 2^-(e+30) / 2 for the area, / 6 for the
+ * volume, plus the final roundings). */
+#define PSGPU_FILTER_CLOSED_ONLY   1u
+#define PSGPU_FILTER_DROP_CAVITIES 2u
+typedef struct PsShellFilter {      /* all zero + no mask: every shell is kept */
+    uint32_t flags;                 /* PSGPU_FILTER_CLOSED_ONLY | PSGPU_FILTER_DROP_CAVITIES */
+    uint32_t minVertices, minTriangles;
+    uint32_t reserved;              /* must be 0 */
+    double   minArea, minAbsVolume; /* finite, >= 0 */
+} PsShellFilter;
+typedef struct PsFilterInfo {
+    uint32_t ctVertices, ctTriangles, ctShells;                /* kept */
+    uint32_t ctInputVertices, ctInputTriangles, ctInputShells; /* the weld's, the shells result's */
+} PsFilterInfo;
+typedef struct PsFilterDevice {     /* valid until the next weld / shells / filter call / destroy */
+    const float*    pos;            /* ctVertices * 3 */
+    const float*    nrm;
+    const float*    col;
+    const uint32_t* tris;           /* ctTriangles * 3, filtered vertex ids */
+    const uint32_t* vertexMap;      /* ctInputVertices */
+    const uint32_t* shellMap;       /* ctInputShells */
+    const PsShell*  shells;         /* ctShells */
+} PsFilterDevice;
+/* Filter the context's weld by the shells of its current psgpu_weld_shells result, on the
+ * context's stream; blocking.  f == NULL means all zero; mask is NULL or maskCount == ctShells
+ * bytes on the host (one upload).  The criteria are evaluated on the device; the host reads
+ * the totals once, at the end.  PSGPU_RET_PARAM_ERROR when there is no valid shells result for
+ * the current weld (psgpu_weld_shells_device's rule), when mask != NULL and maskCount !=
+ * ctShells, for unknown flag bits, reserved != 0, and for a NaN, infinite or negative minArea /
+ * minAbsVolume (a call refused for its arguments leaves an earlier result as it was).  A filter that keeps nothing and a filter of an empty weld succeed with an
+ * empty mesh.  A new psgpu_weld or psgpu_weld_shells invalidates the filter result, as does
+ * whatever invalidates those; a second filter call replaces the first.  The weld's arrays, the
+ * shells and the run are left untouched.  The buffers come with the first call, grow on demand
+ * and go with the weld's: a context that never filters pays nothing.  PSGPU_RET_DEVICE_ERROR if
+ * a kept triangle names a dropped vertex (never on a shells result's own arrays). */
+int  psgpu_weld_filter(psgpu_ctx* ctx, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
+                       PsFilterInfo* info);
+/* The filtered mesh in HBM / on the host (any pointer may be NULL): PSGPU_RET_PARAM_ERROR before
+ * a successful psgpu_weld_filter of the current shells result, and for a shellCapacity below the
+ * kept count. */
+int  psgpu_weld_filter_device(psgpu_ctx* ctx, PsFilterDevice* out);
+int  psgpu_download_weld_filter(psgpu_ctx* ctx, float* pos, float* nrm, float* col, uint32_t* tris,
+                                uint32_t* vertexMap, uint32_t* shellMap, PsShell* shells, uint32_t shellCapacity);
+/* hipEvent times (ms) of the last psgpu_weld_filter with PSGPU_OPT_KERNEL_TIMING set: the whole
+ * call, then one entry per launch (the mask's upload with the first, the two scans as one);
+ * returns the count filled. */
+int  psgpu_weld_filter_times(psgpu_ctx* ctx, float* ms, int maxPhases, const char** names);
+
 /* Per-MPU stats for every MPU in the last processed range (ctMPUs entries). */
 int  psgpu_download_stats(psgpu_ctx* ctx, PsMpuStats* stats);
 /* Scatter the last result into the reference PolyMPUs layout (vMPUs[0..ctMPUs)). */
@@ -654,6 +728,17 @@ int  psgpu_group_weld_shells_device(psgpu_group* g, PsShellsDevice* out);
 int  psgpu_group_download_weld_shells(psgpu_group* g, PsShell* shells, uint32_t capacity, uint32_t* vertexShell,
                                       uint32_t* triShell);
 int  psgpu_group_weld_shells_times(psgpu_group* g, float* ms, int maxPhases, const char** names);
+/* The group's weld filtered by its shells (psgpu_weld_filter's contract, above), on the welding
+ * part's device: PSGPU_RET_PARAM_ERROR unless the group's current weld has a shells result; a
+ * new psgpu_group_weld or psgpu_group_weld_shells invalidates the filter result; the buffers go
+ * with psgpu_group_destroy. */
+int  psgpu_group_weld_filter(psgpu_group* g, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
+                             PsFilterInfo* info);
+int  psgpu_group_weld_filter_device(psgpu_group* g, PsFilterDevice* out);
+int  psgpu_group_download_weld_filter(psgpu_group* g, float* pos, float* nrm, float* col, uint32_t* tris,
+                                      uint32_t* vertexMap, uint32_t* shellMap, PsShell* shells,
+                                      uint32_t shellCapacity);
+int  psgpu_group_weld_filter_times(psgpu_group* g, float* ms, int maxPhases, const char** names);
 int  psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCtMPUs);
 /* Blocking drop-in for PS::SIMDPOLY::Polygonize over every device of the group. */
 int  psgpu_group_polygonize_mpus(psgpu_group* g, float cellsize, const PsSoaBlobPrims* prims,
@@ -709,6 +794,8 @@ static_assert(offsetof(PsMPU, ctFieldEvals) == 21520, "ctFieldEvals offset");
 static_assert(sizeof(PsMpuProcessStats) == 32, "MPUSTATS size (LP64)");
 static_assert(sizeof(PsShell) == 72, "PsShell size");
 static_assert(sizeof(PsShellsInfo) == 80, "PsShellsInfo size");
+static_assert(sizeof(PsShellFilter) == 32, "PsShellFilter size");
+static_assert(sizeof(PsFilterInfo) == 24, "PsFilterInfo size");
 static_assert(offsetof(PsMpuProcessStats, threadID) == 8, "MPUSTATS threadID offset");
 static_assert(offsetof(PsMpuProcessStats, tickStart) == 16, "MPUSTATS tickStart offset");
 static_assert(offsetof(PsMpuProcessStats, tickEnd) == 24, "MPUSTATS tickEnd offset");
@@ -720,6 +807,8 @@ _Static_assert(sizeof(PsSoaBoxMatrices) == 8196, "SOABlobBoxMatrices size");
 _Static_assert(sizeof(PsMPU) == 21524, "MPU size");
 _Static_assert(sizeof(PsShell) == 72, "PsShell size");
 _Static_assert(sizeof(PsShellsInfo) == 80, "PsShellsInfo size");
+_Static_assert(sizeof(PsShellFilter) == 32, "PsShellFilter size");
+_Static_assert(sizeof(PsFilterInfo) == 24, "PsFilterInfo size");
 #endif
 
 #endif /* PARSIP_GPU_H */

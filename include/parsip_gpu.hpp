@@ -205,6 +205,27 @@ struct Shells {
     }
 };
 
+/* A weld filtered by its shells (psgpu_weld_filter, psgpu_group_weld_filter): the kept shells'
+ * vertices and triangles compacted in order, the maps and the kept records, as host copies. */
+struct Filtered {
+    PsFilterInfo info{};
+    std::vector<float> pos, nrm, col;  /* info.ctVertices * 3 each */
+    std::vector<uint32_t> tris;        /* info.ctTriangles * 3, filtered ids */
+    std::vector<uint32_t> vertexMap;   /* info.ctInputVertices: 0xffffffff for a dropped vertex */
+    std::vector<uint32_t> shellMap;    /* info.ctInputShells: 0xffffffff for a dropped shell */
+    std::vector<PsShell> shells;       /* info.ctShells: the kept records, firstVertex remapped */
+    void resize(const PsFilterInfo& i) {
+        info = i;
+        pos.resize(size_t(i.ctVertices) * 3);
+        nrm.resize(size_t(i.ctVertices) * 3);
+        col.resize(size_t(i.ctVertices) * 3);
+        tris.resize(size_t(i.ctTriangles) * 3);
+        vertexMap.resize(i.ctInputVertices);
+        shellMap.resize(i.ctInputShells);
+        shells.resize(i.ctShells);
+    }
+};
+
 /* SimdPoly-shaped adapter (PS_HighPerformanceRender.h:15-33) over a device-resident
  * compact mesh: setModel once per edit, run() per frame, mesh() for GL / export. */
 template <class Prims, class Mats, class Ops>
@@ -256,6 +277,25 @@ public:
     }
     /* The same shells left in HBM (valid until the next weld or shells call). */
     int weldShellsDevice(PsShellsDevice* out) { return psgpu_weld_shells_device(ctx_.get(), out); }
+    /* That weld without the shells a filter drops (psgpu_weld_filter; f == nullptr keeps every
+     * shell, mask is nullptr or one byte per shell).  After weldShells(); PSGPU_RET_PARAM_ERROR
+     * without a shells result of the current weld (out is left empty). */
+    using Filtered = psgpu::Filtered;
+    int weldFilter(Filtered* out, const PsShellFilter* f = nullptr, const uint8_t* mask = nullptr,
+                   uint32_t maskCount = 0) {
+        if (!ctx_.ok()) return ctx_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Filtered();
+        PsFilterInfo info;
+        const int rc = psgpu_weld_filter(ctx_.get(), f, mask, maskCount, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_download_weld_filter(ctx_.get(), out->pos.data(), out->nrm.data(), out->col.data(),
+                                          out->tris.data(), out->vertexMap.data(), out->shellMap.data(),
+                                          out->shells.data(), info.ctShells);
+    }
+    /* The same filtered mesh left in HBM (valid until the next weld, shells or filter call). */
+    int weldFilterDevice(PsFilterDevice* out) { return psgpu_weld_filter_device(ctx_.get(), out); }
     Context& context() { return ctx_; }
 
 private:
@@ -401,6 +441,23 @@ public:
                                                 out->vertexShell.data(), out->triShell.data());
     }
     int weldShellsDevice(PsShellsDevice* out) { return psgpu_group_weld_shells_device(grp_.get(), out); }
+    /* That weld without the shells a filter drops (psgpu_group_weld_filter): PSGPU_RET_PARAM_ERROR
+     * without a shells result of the current weld (out is left empty). */
+    using Filtered = psgpu::Filtered;
+    int weldFilter(Filtered* out, const PsShellFilter* f = nullptr, const uint8_t* mask = nullptr,
+                   uint32_t maskCount = 0) {
+        if (!grp_.ok()) return grp_.status();
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Filtered();
+        PsFilterInfo info;
+        const int rc = psgpu_group_weld_filter(grp_.get(), f, mask, maskCount, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_group_download_weld_filter(grp_.get(), out->pos.data(), out->nrm.data(), out->col.data(),
+                                                out->tris.data(), out->vertexMap.data(), out->shellMap.data(),
+                                                out->shells.data(), info.ctShells);
+    }
+    int weldFilterDevice(PsFilterDevice* out) { return psgpu_group_weld_filter_device(grp_.get(), out); }
     const PsMeshInfo& info() const { return info_; }
     const PsSoaBlobPrims& prims() const { return prims_; }
     const PsSoaBlobOps& ops() const { return ops_; }

@@ -524,6 +524,7 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
     WeldState& W = g->weld;
     W.doneSeq = ~0ull;
     W.shells.valid = false;
+    W.filter.valid = false;
     memset(&W.info, 0, sizeof(W.info));
     W.info.ctInputVertices = T.ctVertices;
     W.info.ctTriangles = T.ctTriangles;
@@ -634,6 +635,33 @@ int psgpu_group_download_weld_shells(psgpu_group* g, PsShell* shells, uint32_t c
 
 int psgpu_group_weld_shells_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
     return g ? shells_times(g->weld, ms, maxPhases, names) : 0;
+}
+
+// The filter of the group's weld by its shells (psgpu_filter.hip), where the shells ran.
+int psgpu_group_weld_filter(psgpu_group* g, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
+                            PsFilterInfo* info) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    psgpu_ctx* dst = g->parts[g->weldPart];
+    PSGPU_CHECK(hipSetDevice(dst->device));
+    return filter_run(g->weld, g->gatherStream ? g->gatherStream : dst->stream, dst->timing != 0, f, mask, maskCount,
+                      info);
+}
+
+int psgpu_group_weld_filter_device(psgpu_group* g, PsFilterDevice* out) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    return filter_device(g->weld, out);
+}
+
+int psgpu_group_download_weld_filter(psgpu_group* g, float* pos, float* nrm, float* col, uint32_t* tris,
+                                     uint32_t* vertexMap, uint32_t* shellMap, PsShell* shells,
+                                     uint32_t shellCapacity) {
+    if (!group_welded(g)) return PSGPU_RET_PARAM_ERROR;
+    PSGPU_CHECK(hipSetDevice(g->parts[g->weldPart]->device));
+    return filter_download(g->weld, pos, nrm, col, tris, vertexMap, shellMap, shells, shellCapacity);
+}
+
+int psgpu_group_weld_filter_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
+    return g ? filter_times(g->weld, ms, maxPhases, names) : 0;
 }
 
 int psgpu_group_export_polympus(psgpu_group* g, PsMPU* mpus, uint32_t capacity, uint32_t* outCt) {

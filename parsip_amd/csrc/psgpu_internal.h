@@ -50,6 +50,29 @@ struct ShellsState {
     float lastMs[kShellsPhases] = {};
 };
 
+// The welded mesh filtered by shell (psgpu_filter.hip): the stable compaction of the shells
+// that pass psgpu_weld_filter's criteria.  Part of the weld and the shells result it was made
+// from; its buffers come with the first psgpu_weld_filter, grow on demand and go with the weld's.
+constexpr int kFilterPhases = 7;  // psgpu_weld_filter_times: the whole call, then its six steps
+struct FilterState {
+    DevBuf<uint8_t> mask;        // per shell: the caller's mask, uploaded
+    DevBuf<uint8_t> keep;        // per shell: it stays
+    DevBuf<uint64_t> shellCnt;   // per block of shells: kept, scanned
+    DevBuf<uint64_t> blockCnt;   // per block of vertices and triangles: kept | kept << 32, scanned
+    DevBuf<uint32_t> ctl;        // error word, then the kept shells, vertices and triangles
+    DevBuf<float> pos;           // the filtered mesh
+    DevBuf<float> nrm;
+    DevBuf<float> col;
+    DevBuf<uint32_t> tris;
+    DevBuf<uint32_t> vertexMap;  // per welded vertex
+    DevBuf<uint32_t> shellMap;   // per shell
+    DevBuf<PsShell> shells;      // the kept shells' records
+    bool valid = false;          // holds a filter of the shells beside it (a new weld or shells call clears it)
+    PsFilterInfo info{};
+    hipEvent_t ev[kFilterPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: before the first step, after each
+    float lastMs[kFilterPhases] = {};
+};
+
 struct WeldState {
     DevBuf<unsigned char> table;  // open-addressing table: edge ids (8 B a slot), then minima (4 B a slot)
     DevBuf<uint32_t> rep;         // per input vertex: its representative (the smallest index on its edge)
@@ -65,6 +88,7 @@ struct WeldState {
     hipEvent_t ev[kWeldPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: around the launches
     float lastMs[kWeldPhases] = {};
     ShellsState shells;               // psgpu_weld_shells of this weld
+    FilterState filter;               // psgpu_weld_filter of this weld and those shells
 };
 
 }  // namespace psgpu
@@ -231,6 +255,16 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info);
 int shells_device(const WeldState& W, PsShellsDevice* out);
 int shells_download(const WeldState& W, PsShell* shells, uint32_t capacity, uint32_t* vertexShell, uint32_t* triShell);
 int shells_times(const WeldState& W, float* ms, int maxPhases, const char** names);
+// The filter of a weld by its shells (psgpu_filter.hip), for a context's weld and a group's
+// alike; the weld's device is current.  filter_run: W holds a finished weld; PARAM_ERROR unless
+// W.shells.valid; blocking on s; `timed` records W.filter.lastMs.  The others serve W.filter once
+// filter_run has succeeded on the current shells (W.filter.valid).
+int filter_run(WeldState& W, hipStream_t s, bool timed, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
+               PsFilterInfo* info);
+int filter_device(const WeldState& W, PsFilterDevice* out);
+int filter_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap,
+                    uint32_t* shellMap, PsShell* shells, uint32_t shellCapacity);
+int filter_times(const WeldState& W, float* ms, int maxPhases, const char** names);
 // The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.

@@ -516,6 +516,7 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     ShellsState& S = W.shells;
     const uint32_t V = W.info.ctVertices, T = W.info.ctTriangles;
     S.valid = false;
+    W.filter.valid = false;
     memset(&S.info, 0, sizeof(S.info));
     for (float& ms : S.lastMs) ms = 0.0f;
     if (V == 0) {  // an empty weld: no shell, nothing to launch

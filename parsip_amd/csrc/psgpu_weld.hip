@@ -427,11 +427,13 @@ bool weld_run_ready(const psgpu_ctx* c) {
 }
 
 void weld_state_free(WeldState& W) {
+    for (hipEvent_t e : W.filter.ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : W.shells.ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : W.ev)
         if (e) (void)hipEventDestroy(e);
-    W = WeldState{};  // releases the weld's buffers and the shells'
+    W = WeldState{};  // releases the weld's buffers, the shells' and the filter's
 }
 
 void weld_free(psgpu_ctx* c) { weld_state_free(c->weld); }
@@ -520,6 +522,7 @@ int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
     const uint32_t V = c->info.ctVertices, T = c->info.ctTriangles;
     W.doneSeq = ~0ull;
     W.shells.valid = false;
+    W.filter.valid = false;
     memset(&W.info, 0, sizeof(W.info));
     W.info.ctInputVertices = V;
     W.info.ctTriangles = T;

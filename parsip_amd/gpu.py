@@ -79,6 +79,24 @@ class PsShellsDevice(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("shells", "vertexShell", "triShell")]
 
 
+class PsShellFilter(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("minVertices", ctypes.c_uint32), ("minTriangles", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("minArea", ctypes.c_double), ("minAbsVolume", ctypes.c_double)]
+
+
+class PsFilterInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("ctVertices", "ctTriangles", "ctShells", "ctInputVertices",
+                                                "ctInputTriangles", "ctInputShells")]
+
+
+class PsFilterDevice(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "nrm", "col", "tris", "vertexMap", "shellMap", "shells")]
+
+
+FILTER_CLOSED_ONLY = meshio.FILTER_CLOSED_ONLY
+FILTER_DROP_CAVITIES = meshio.FILTER_DROP_CAVITIES
+
+assert ctypes.sizeof(PsShellFilter) == meshio.SHELL_FILTER_DTYPE.itemsize == 32 and ctypes.sizeof(PsFilterInfo) == 24
 assert ctypes.sizeof(PsShell) == meshio.SHELL_DTYPE.itemsize == 72
 assert ctypes.sizeof(PsShellsInfo) == meshio.SHELLS_INFO_DTYPE.itemsize == 80
 
@@ -104,6 +122,9 @@ EXPORTED_SYMBOLS = [
     "psgpu_weld_shells", "psgpu_weld_shells_device", "psgpu_download_weld_shells", "psgpu_weld_shells_times",
     "psgpu_group_weld_shells", "psgpu_group_weld_shells_device", "psgpu_group_download_weld_shells",
     "psgpu_group_weld_shells_times",
+    "psgpu_weld_filter", "psgpu_weld_filter_device", "psgpu_download_weld_filter", "psgpu_weld_filter_times",
+    "psgpu_group_weld_filter", "psgpu_group_weld_filter_device", "psgpu_group_download_weld_filter",
+    "psgpu_group_weld_filter_times",
 ]
 
 OPT_KERNEL_TIMING = 1
@@ -229,6 +250,14 @@ def load(build_if_missing: bool = True):
         "psgpu_group_weld_shells_device": ([vp, ctypes.POINTER(PsShellsDevice)], i32),
         "psgpu_group_download_weld_shells": ([vp, vp, ctypes.c_uint32, vp, vp], i32),
         "psgpu_group_weld_shells_times": ([vp, vp, i32, vp], i32),
+        "psgpu_weld_filter": ([vp, vp, vp, u32, ctypes.POINTER(PsFilterInfo)], i32),
+        "psgpu_weld_filter_device": ([vp, ctypes.POINTER(PsFilterDevice)], i32),
+        "psgpu_download_weld_filter": ([vp, vp, vp, vp, vp, vp, vp, vp, u32], i32),
+        "psgpu_weld_filter_times": ([vp, vp, i32, vp], i32),
+        "psgpu_group_weld_filter": ([vp, vp, vp, u32, ctypes.POINTER(PsFilterInfo)], i32),
+        "psgpu_group_weld_filter_device": ([vp, ctypes.POINTER(PsFilterDevice)], i32),
+        "psgpu_group_download_weld_filter": ([vp, vp, vp, vp, vp, vp, vp, vp, u32], i32),
+        "psgpu_group_weld_filter_times": ([vp, vp, i32, vp], i32),
         "psgpu_vertex_queue": ([vp, vp, vp, u32], i32),
         "psgpu_mpu_masks": ([vp, vp, vp, u32], i32),
         "psgpu_live_bricks": ([vp, vp, u32, vp], i32),
@@ -392,6 +421,26 @@ def _weld_shells(L, handle, prefix: str) -> meshio.Shells:
     _check(getattr(L, prefix + "download_weld_shells")(handle, shells.ctypes.data, info.ctShells, vs.ctypes.data,
                                                         ts.ctypes.data), prefix + "download_weld_shells")
     return meshio.Shells(shells, np.frombuffer(bytes(info), meshio.SHELLS_INFO_DTYPE).copy().reshape(()), vs, ts)
+
+
+def _weld_filter(L, handle, prefix: str, criteria, mask) -> meshio.FilteredMesh:
+    """psgpu_weld_filter / psgpu_group_weld_filter and the download, as meshio.filter_shells returns them."""
+    c = meshio.shell_filter(criteria)
+    m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    info = PsFilterInfo()
+    _check(getattr(L, prefix + "weld_filter")(handle, c.ctypes.data, None if m is None else m.ctypes.data,
+                                              0 if m is None else m.size, ctypes.byref(info)), prefix + "weld_filter")
+    V, T = info.ctVertices, info.ctTriangles
+    pos, nrm, col = (np.zeros((V, 3), np.float32) for _ in range(3))
+    tris = np.zeros((T, 3), np.uint32)
+    vmap = np.zeros(info.ctInputVertices, np.uint32)
+    smap = np.zeros(info.ctInputShells, np.uint32)
+    shells = np.zeros(info.ctShells, meshio.SHELL_DTYPE)
+    _check(getattr(L, prefix + "download_weld_filter")(handle, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data,
+                                                        tris.ctypes.data, vmap.ctypes.data, smap.ctypes.data,
+                                                        shells.ctypes.data, info.ctShells),
+           prefix + "download_weld_filter")
+    return meshio.FilteredMesh(pos, nrm, col, tris, vmap, smap, shells)
 
 
 def _shells_times(fn, handle) -> dict:
@@ -625,6 +674,23 @@ class Polygonizer:
         """hipEvent times (ms) of the last ``weld_shells()`` (OPT_KERNEL_TIMING): the call and its steps."""
         return _shells_times(self._L.psgpu_weld_shells_times, self._ctx)
 
+    def weld_filter(self, criteria=None, mask=None) -> meshio.FilteredMesh:
+        """psgpu_weld_filter on the current shells (``weld_shells()`` first): the welded mesh
+        without the shells that fail ``criteria`` (what ``meshio.shell_filter`` takes) or have a
+        zero in ``mask``, compacted in order on the device; the same bytes as
+        ``meshio.filter_shells`` of the weld's and the shells' downloads."""
+        return _weld_filter(self._L, self._ctx, "psgpu_", criteria, mask)
+
+    def weld_filter_device(self) -> PsFilterDevice:
+        """Device pointers of the last ``weld_filter()`` (valid until the next weld, shells or filter call)."""
+        d = PsFilterDevice()
+        _check(self._L.psgpu_weld_filter_device(self._ctx, ctypes.byref(d)), "psgpu_weld_filter_device")
+        return d
+
+    def weld_filter_times(self) -> dict:
+        """hipEvent times (ms) of the last ``weld_filter()`` (OPT_KERNEL_TIMING): the call and its launches."""
+        return _shells_times(self._L.psgpu_weld_filter_times, self._ctx)
+
     def mpu_costs(self) -> np.ndarray:
         """Per-MPU lane-evaluations of the last run (balances ranges across devices)."""
         info = self.finish()
@@ -846,6 +912,20 @@ class Group:
     def weld_shells_times(self) -> dict:
         """hipEvent times (ms) of the last ``weld_shells()`` (OPT_KERNEL_TIMING on the group)."""
         return _shells_times(self._L.psgpu_group_weld_shells_times, self._g)
+
+    def weld_filter(self, criteria=None, mask=None) -> meshio.FilteredMesh:
+        """psgpu_group_weld_filter on the group's current shells: as ``Polygonizer.weld_filter()``."""
+        return _weld_filter(self._L, self._g, "psgpu_group_", criteria, mask)
+
+    def weld_filter_device(self) -> PsFilterDevice:
+        """Device pointers of the last ``weld_filter()`` (valid until the next weld, shells or filter call)."""
+        d = PsFilterDevice()
+        _check(self._L.psgpu_group_weld_filter_device(self._g, ctypes.byref(d)), "psgpu_group_weld_filter_device")
+        return d
+
+    def weld_filter_times(self) -> dict:
+        """hipEvent times (ms) of the last ``weld_filter()`` (OPT_KERNEL_TIMING on the group)."""
+        return _shells_times(self._L.psgpu_group_weld_filter_times, self._g)
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info, _ = self.finish()

@@ -348,6 +348,102 @@ def shells(pos, tris=None) -> Shells:
     return Shells(out, info, vs.astype(np.uint32), ts.astype(np.uint32))
 
 
+# PsShellFilter (include/parsip_gpu.h), field for field, and its flags
+SHELL_FILTER_DTYPE = np.dtype([("flags", "<u4"), ("minVertices", "<u4"), ("minTriangles", "<u4"), ("reserved", "<u4"),
+                               ("minArea", "<f8"), ("minAbsVolume", "<f8")])
+assert SHELL_FILTER_DTYPE.itemsize == 32
+FILTER_CLOSED_ONLY = 1
+FILTER_DROP_CAVITIES = 2
+DROPPED = 0xFFFFFFFF   # vertex_map / shell_map of what a filter drops
+
+
+def shell_filter(criteria=None, **fields) -> np.ndarray:
+    """A PsShellFilter as a 0-d SHELL_FILTER_DTYPE: ``criteria`` (None: all zero; a mapping or
+    such an array) updated by ``fields``; ValueError on what psgpu_weld_filter refuses (an
+    unknown field or flag bit, reserved != 0, a NaN, infinite or negative minArea / minAbsVolume)."""
+    c = np.zeros((), SHELL_FILTER_DTYPE)
+    if criteria is not None and not isinstance(criteria, dict):
+        criteria = {k: criteria[k] for k in SHELL_FILTER_DTYPE.names}
+    for k, v in dict(criteria or {}, **fields).items():
+        if k not in SHELL_FILTER_DTYPE.names:
+            raise ValueError(f"PsShellFilter has no field {k!r}")
+        c[k] = v
+    if int(c["flags"]) & ~(FILTER_CLOSED_ONLY | FILTER_DROP_CAVITIES) or c["reserved"] != 0:
+        raise ValueError("unknown filter flags, or reserved != 0")
+    for k in ("minArea", "minAbsVolume"):
+        if not (np.isfinite(c[k]) and c[k] >= 0.0):
+            raise ValueError(f"{k} must be finite and >= 0")
+    return c
+
+
+@dataclass
+class FilteredMesh:
+    """What `filter_shells` returns (and, from the device, `gpu.Polygonizer.weld_filter`)."""
+    pos: np.ndarray         # (Vf, 3) f32: the kept vertices, in order
+    nrm: np.ndarray
+    col: np.ndarray
+    tris: np.ndarray        # (Tf, 3) u32: the kept triangles, in order, filtered vertex ids
+    vertex_map: np.ndarray  # (V,) u32: filtered id of every input vertex, DROPPED if it is dropped
+    shell_map: np.ndarray   # (S,) u32: new index of every shell, DROPPED if it is dropped
+    shells: np.ndarray      # (Sf,) SHELL_DTYPE: the kept records, firstVertex remapped
+
+    def tobytes(self) -> bytes:
+        return b"".join(np.ascontiguousarray(a).tobytes() for a in
+                        (self.pos, self.nrm, self.col, self.tris, self.vertex_map, self.shell_map, self.shells))
+
+
+def shells_kept(shells: np.ndarray, criteria=None, mask=None) -> np.ndarray:
+    """psgpu_weld_filter's rule (parsip_gpu.h): which PsShell records a filter keeps, as bools;
+    plain IEEE comparisons of the fields as stored."""
+    c = shell_filter(criteria)
+    sh = np.asarray(shells, SHELL_DTYPE)
+    keep = np.ones(len(sh), bool)
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != (len(sh),):
+            raise ValueError(f"the mask has {m.size} entries, there are {len(sh)} shells")
+        keep &= m != 0
+    closed = ((sh["ctTriangles"] > 0) & (sh["ctOpenEdges"] == 0) & (sh["ctFlippedEdges"] == 0) &
+              (sh["ctNonManifoldEdges"] == 0))
+    keep &= (sh["ctVertices"] >= c["minVertices"]) & (sh["ctTriangles"] >= c["minTriangles"])
+    keep &= (sh["area"] >= c["minArea"]) & (np.abs(sh["volume"]) >= c["minAbsVolume"])
+    if int(c["flags"]) & FILTER_CLOSED_ONLY:
+        keep &= closed
+    if int(c["flags"]) & FILTER_DROP_CAVITIES:
+        keep &= ~(closed & (sh["volume"] < 0.0))
+    return keep
+
+
+def _compact_map(keep: np.ndarray) -> np.ndarray:
+    """Stable compaction: the new index of every kept element, DROPPED for the others."""
+    out = np.full(len(keep), DROPPED, np.uint32)
+    out[keep] = np.arange(int(keep.sum()), dtype=np.uint32)
+    return out
+
+
+def filter_shells(pos, nrm, col, tris, shells: Shells, criteria=None, mask=None) -> FilteredMesh:
+    """The mesh without the shells a filter drops: the host form of psgpu_weld_filter, same rule
+    (parsip_gpu.h), same bytes.  ``shells`` is the mesh's `Shells` (`shells(pos, tris)`, or a
+    device download), ``criteria`` what `shell_filter` takes, ``mask`` one entry per shell.
+    Kept vertices and triangles stay in order; the kept records keep the measures of the
+    unfiltered mesh."""
+    p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(col, np.float32).reshape(-1, 3)
+    t = np.asarray(tris).astype(np.int64).reshape(-1, 3)
+    if not (len(n) == len(c) == len(p) == len(shells.vertex_shell)) or len(t) != len(shells.tri_shell):
+        raise ValueError("the shells are not those of this mesh")
+    keep = shells_kept(shells.shells, criteria, mask)
+    kv, kt = keep[shells.vertex_shell], keep[shells.tri_shell]
+    vertex_map = _compact_map(kv)
+    ftris = vertex_map[t[kt]].reshape(-1, 3)
+    if (ftris == DROPPED).any():
+        raise ValueError("a kept triangle names a dropped vertex")
+    out = np.asarray(shells.shells, SHELL_DTYPE)[keep].copy()
+    out["firstVertex"] = vertex_map[out["firstVertex"]]
+    return FilteredMesh(p[kv], n[kv], c[kv], ftris, vertex_map, _compact_map(keep), out)
+
+
 def _fmt(a) -> str:
     return " ".join(f"{float(x):.9g}" for x in a)
 

@@ -26,6 +26,15 @@ the weld re-measured in the same process and the host route download of the weld
 meshio.shells.  Output committed as profiles/shells_c3.txt (DESIGN.md §6 "Shells").
 
     python3 tools/weld_bench.py [CONFIG] --shells
+
+With --filter the filter of the weld by its shells is timed (psgpu_weld_filter: hipEvents
+through psgpu_weld_filter_times, the whole call and each launch, median of 20 after 5 warm-ups)
+with minTriangles midway between the two largest shells (the body stays, the bits around it go),
+beside the weld re-measured in the same process and the host route: downloads of the weld and
+the shells + meshio.filter_shells.  Output committed as profiles/filter_c3.txt (DESIGN.md §6
+"Filter").
+
+    python3 tools/weld_bench.py [CONFIG] --filter
 """
 import argparse
 import os
@@ -169,12 +178,74 @@ def shells_main(name):
     poly.close()
 
 
+def filter_main(name):
+    model, cs, _ = synth.make_config(name)
+    poly = gpu.Polygonizer(0)
+    poly.set_option(gpu.OPT_KERNEL_TIMING, 1)
+    poly.set_model(model)
+    info = poly.run(cs)
+    print(f"{name}: cellsize {cs}, {info.ctMPUs} MPUs, {info.ctVertices} vertices, {info.ctTriangles} triangles")
+    rows, wall, winfo = timed_welds(poly.weld_info, poly.weld_times)
+    print(f"device weld, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms):")
+    print_phases(rows)
+    print(f"  {'psgpu_weld call, wall':28s} {statistics.median(wall):8.4f}")
+    wmed = {ph: statistics.median([r[ph] for r in rows]) for ph in rows[0]}
+    weld_ms, moved_ms = wmed["weld total"], wmed["k_weld_emit"] + wmed["k_weld_map"]
+
+    sh = poly.weld_shells()
+    by_size = np.sort(sh.shells["ctTriangles"])[::-1]
+    cut = int((int(by_size[0]) + int(by_size[1] if len(by_size) > 1 else 0)) // 2)
+    criteria = meshio.shell_filter(minTriangles=cut)
+    print(f"shells: {len(sh.shells)}, triangles per shell {by_size[:10].tolist()}; filter: minTriangles {cut}")
+    L = gpu.load()
+    finfo = gpu.PsFilterInfo()
+
+    def filter_info():
+        rc = L.psgpu_weld_filter(poly._ctx, criteria.ctypes.data, None, 0, finfo)
+        assert rc == soa.RET_SUCCESS, rc
+        return finfo
+
+    rows, wall, _ = timed_welds(filter_info, poly.weld_filter_times)
+    print(f"device filter, median of {REPS} after {WARMUP} warm-ups (hipEvents, ms):")
+    print_phases(rows)
+    print(f"  {'psgpu_weld_filter call, wall':28s} {statistics.median(wall):8.4f}   (launches + wait + the totals' read-back)")
+    med = {ph: statistics.median([r[ph] for r in rows]) for ph in rows[0]}
+    dev_ms = med["filter total"]
+    top = max((ph for ph in med if ph != "filter total"), key=lambda ph: med[ph])
+    print(f"  largest launch: {top} ({med[top]:.4f} ms, {100 * med[top] / dev_ms:.0f} % of the total)")
+    compact = med["k_filter_emit"] + med["k_filter_tris"]
+    print(f"  k_filter_emit + k_filter_tris: {compact:.4f} ms = {compact / moved_ms:.2f}x k_weld_emit + k_weld_map "
+          f"({moved_ms:.4f} ms); filter total / (k_weld_emit + k_weld_map): {dev_ms / moved_ms:.2f}x")
+    print(f"filter: {finfo.ctInputShells} -> {finfo.ctShells} shells, {finfo.ctInputVertices} -> {finfo.ctVertices} "
+          f"vertices, {finfo.ctInputTriangles} -> {finfo.ctTriangles} triangles")
+    f = poly.weld_filter(criteria)
+
+    ts, ref = [], None
+    for _ in range(HOST_REPS):
+        t0 = time.perf_counter()
+        w = poly.weld()
+        hs = poly.weld_shells()
+        t1 = time.perf_counter()
+        ref = meshio.filter_shells(w.pos, w.nrm, w.col, w.tris, hs, criteria)
+        ts.append(((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
+    dl_ms, host_ms = (statistics.median(c) for c in zip(*ts))
+    print(f"host route, median of {HOST_REPS} (wall, ms; the filtered mesh is not uploaded again):")
+    print(f"  {'weld() + weld_shells() (calls + downloads)':44s} {dl_ms:10.2f}")
+    print(f"  {'... + meshio.filter_shells':44s} {host_ms:10.2f}")
+    print(f"device filter == meshio.filter_shells: {f.tobytes() == ref.tobytes()}")
+    print(f"filter / weld on the device: {dev_ms / weld_ms:.2f}x; host route / device filter: {host_ms / dev_ms:.0f}x")
+    poly.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", nargs="?", default="C3")
     ap.add_argument("--parts", type=int, default=0, help="run as a Group of N parts on device 0 and time psgpu_group_weld")
     ap.add_argument("--shells", action="store_true", help="time psgpu_weld_shells on the weld")
+    ap.add_argument("--filter", action="store_true", help="time psgpu_weld_filter on the weld and its shells")
     args = ap.parse_args()
+    if args.filter:
+        return filter_main(args.config)
     if args.shells:
         return shells_main(args.config)
     if args.parts > 0:
