@@ -109,4 +109,9 @@ struct PinnedBuf {
     }
 };
 
+// `count` elements of `size` bytes to the host, if the caller wants them and there are any.
+inline hipError_t download_if(void* dst, const void* src, size_t count, size_t size) {
+    return dst && count ? hipMemcpy(dst, src, count * size, hipMemcpyDeviceToHost) : hipSuccess;
+}
+
 }  // namespace psgpu

@@ -75,8 +75,7 @@ struct psgpu_group {
     DevBuf<uint64_t> gEdge;            // the gathered vertices' edge ids, beside the gathered mesh
     std::vector<DevBuf<uint64_t>> partEdge;  // each part's edge ids on its own device (k_weld_edges)
     std::vector<hipEvent_t> partEdgeEv;  // ... and the event the gather stream waits for
-    hipEvent_t weldEv[kGroupWeldPhases] = {};
-    float weldMs[kGroupWeldPhases] = {};
+    PhaseTimes<kGroupWeldPhases> weldTimes;
 };
 
 namespace {
@@ -100,10 +99,7 @@ void free_weld(psgpu_group* g) {
         (void)hipSetDevice(g->parts[g->weldPart]->device);
         weld_state_free(g->weld);  // (hipFree waits for the device)
         g->gEdge.release();
-        for (hipEvent_t& e : g->weldEv) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+        g->weldTimes.free();
     }
     for (size_t p = 0; p < g->partEdge.size(); ++p) {
         if (!g->partEdge[p] && !g->partEdgeEv[p]) continue;
@@ -516,24 +512,14 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
         const psgpu_ctx* c = g->parts[p];
         // the part still holds the run the group collected (not one made through its own pointer)
         if (!weld_run_ready(c) || c->runSeq != g->partSeq[p]) return PSGPU_RET_PARAM_ERROR;
-        for (int a = 0; a < 3; ++a)
-            if (7ull * c->dims[a] >= (1ull << 20)) return PSGPU_RET_PARAM_ERROR;  // 20 bits a coordinate
+        if (!weld_lattice_fits(c->dims)) return PSGPU_RET_PARAM_ERROR;
     }
     if (g->weldPart != dstPart) free_weld(g);
     g->weldPart = dstPart;
     WeldState& W = g->weld;
-    W.doneSeq = ~0ull;
-    W.shells.valid = false;
-    W.filter.valid = false;
-    memset(&W.info, 0, sizeof(W.info));
-    W.info.ctInputVertices = T.ctVertices;
-    W.info.ctTriangles = T.ctTriangles;
-    for (float& ms : g->weldMs) ms = 0.0f;
-    if (T.ctVertices == 0) {  // nothing to launch: an empty mesh welds to an empty mesh
-        W.doneSeq = g->runSeq;
-        if (info) *info = W.info;
-        return PSGPU_RET_SUCCESS;
-    }
+    PhaseTimes<kGroupWeldPhases>& times = g->weldTimes;
+    times.clear();
+    if (!weld_begin(W, T.ctVertices, T.ctTriangles, g->runSeq, info)) return PSGPU_RET_SUCCESS;
     if (g->partEdge.size() != n) {
         g->partEdge.resize(n);  // (empty before: free_weld clears both)
         g->partEdgeEv.assign(n, nullptr);
@@ -552,37 +538,24 @@ int psgpu_group_weld(psgpu_group* g, int dstPart, PsWeldInfo* info) {
     }
     psgpu_ctx* dst = g->parts[dstPart];
     PSGPU_CHECK(hipSetDevice(dst->device));
-    const bool timed = dst->timing != 0;
-    if (timed)
-        for (hipEvent_t& e : g->weldEv)
-            if (!e) PSGPU_CHECK(hipEventCreate(&e));
+    PSGPU_CHECK(times.begin(dst->timing != 0));
     PSGPU_CHECK(g->gEdge.reserve(T.ctVertices, Growth::ByHalf));
-    rc = gather_enqueue(g, dstPart, T, timed ? g->weldEv[0] : nullptr);
+    rc = gather_enqueue(g, dstPart, T, times.take());
     if (rc != PSGPU_RET_SUCCESS) return rc;
     hipStream_t s = g->gatherStream;
-    if (timed) PSGPU_CHECK(hipEventRecord(g->weldEv[1], s));
+    PSGPU_CHECK(times.mark(s));
     for (size_t p = 0; p < n; ++p) {
         if (!g->info[p].ctVertices) continue;
         PSGPU_CHECK(hipStreamWaitEvent(s, g->partEdgeEv[p], 0));
         PSGPU_CHECK(hipMemcpyPeerAsync(g->gEdge + g->vBase[p], dst->device, g->partEdge[p], g->parts[p]->device,
                                        (size_t)g->info[p].ctVertices * sizeof(uint64_t), s));
     }
-    if (timed) PSGPU_CHECK(hipEventRecord(g->weldEv[2], s));
-    WeldGathered in{g->gPos, g->gNrm, g->gCol, g->gTris, g->gEdge, T.ctVertices, T.ctTriangles};
-    uint64_t totals = 0;
-    rc = weld_gathered(W, in, s, timed ? g->weldEv + 3 : nullptr, &totals);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    PSGPU_CHECK(hipStreamSynchronize(s));
-    if (timed) {
-        (void)hipEventElapsedTime(&g->weldMs[0], g->weldEv[0], g->weldEv[kGroupWeldPhases - 1]);
-        for (int k = 1; k < kGroupWeldPhases; ++k)
-            (void)hipEventElapsedTime(&g->weldMs[k], g->weldEv[k - 1], g->weldEv[k]);
-    }
-    W.info.ctVertices = (uint32_t)totals;
-    W.info.ctSeamVertices = (uint32_t)(totals >> 32);
-    W.doneSeq = g->runSeq;
-    if (info) *info = W.info;
-    return PSGPU_RET_SUCCESS;
+    // the mark that ends the copies' phase is weld_enqueue's first
+    const WeldInput in{g->gPos, g->gNrm, g->gCol, g->gTris, T.ctVertices, T.ctTriangles, g->gEdge, nullptr};
+    rc = weld_enqueue(W, in, s, times.rest());
+    if (rc == PSGPU_RET_SUCCESS) rc = weld_end(W, s, g->runSeq, info);
+    if (rc == PSGPU_RET_SUCCESS) times.collect();
+    return rc;
 }
 
 // the group's current run has been welded
@@ -603,13 +576,7 @@ int psgpu_group_download_weld(psgpu_group* g, float* pos, float* nrm, float* col
 }
 
 int psgpu_group_weld_times(psgpu_group* g, float* ms, int maxPhases, const char** names) {
-    if (!g) return 0;
-    const int n = std::min(maxPhases, kGroupWeldPhases);
-    for (int k = 0; k < n; ++k) {
-        if (ms) ms[k] = g->weldMs[k];
-        if (names) names[k] = kGroupWeldPhaseNames[k];
-    }
-    return n;
+    return g ? g->weldTimes.report(ms, maxPhases, names, kGroupWeldPhaseNames) : 0;
 }
 
 // The shells of the group's weld (psgpu_shells.hip), on the welding part's device and the

@@ -965,7 +965,7 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->tier2Fut = JitFuture();
     c->jit.reset();
     c->jit1.reset();
-    weld_free(c);
+    weld_state_free(c->weld);
     for (int i = 0; i <= kNumKernels; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t e : c->exportEv)

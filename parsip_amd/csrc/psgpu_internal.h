@@ -15,14 +15,12 @@
 #include "psgpu_buf.h"
 #include "psgpu_jit.h"
 #include "psgpu_model.h"
+#include "psgpu_phase_times.h"
 #include "psgpu_plan.h"
 #include "psgpu_pool.h"
 
 namespace psgpu {
 constexpr int kNumKernels = 4;
-}  // namespace psgpu
-
-namespace psgpu {
 constexpr int kExportPieces = 16;  // at most, in the blocking export (psgpu_host.cpp export_stage)
 constexpr size_t kExportPieceBytes = 1u << 20;  // its target piece size
 
@@ -46,8 +44,7 @@ struct ShellsState {
     DevBuf<PsShell> shells;
     bool valid = false;              // holds the shells of the weld beside it (a new weld clears it)
     PsShellsInfo info{};
-    hipEvent_t ev[kShellsPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: before the first step, after each
-    float lastMs[kShellsPhases] = {};
+    PhaseTimes<kShellsPhases> times;
 };
 
 // The welded mesh filtered by shell (psgpu_filter.hip): the stable compaction of the shells
@@ -69,8 +66,7 @@ struct FilterState {
     DevBuf<PsShell> shells;      // the kept shells' records
     bool valid = false;          // holds a filter of the shells beside it (a new weld or shells call clears it)
     PsFilterInfo info{};
-    hipEvent_t ev[kFilterPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: before the first step, after each
-    float lastMs[kFilterPhases] = {};
+    PhaseTimes<kFilterPhases> times;
 };
 
 struct WeldState {
@@ -85,8 +81,7 @@ struct WeldState {
     DevBuf<uint32_t> tris;
     uint64_t doneSeq = ~0ull;        // psgpu_ctx::runSeq of the run the buffers hold the weld of
     PsWeldInfo info{};
-    hipEvent_t ev[kWeldPhases] = {};  // PSGPU_OPT_KERNEL_TIMING: around the launches
-    float lastMs[kWeldPhases] = {};
+    PhaseTimes<kWeldPhases> times;    // a context's weld (a group times its own phases)
     ShellsState shells;               // psgpu_weld_shells of this weld
     FilterState filter;               // psgpu_weld_filter of this weld and those shells
 };
@@ -212,34 +207,39 @@ struct psgpu_ctx {
     psgpu::WeldState weld;
 };
 
-
 namespace psgpu {
 // HIP error -> library return code (prints the failing call).
 int hip_fail(hipError_t e, const char* what);
 // Make the context's device current on the calling thread.
 int set_device(psgpu_ctx* c);
-// Free the weld's buffers and events (psgpu_weld.hip); the context's device is current.
-void weld_free(psgpu_ctx* c);
-// The same for a weld state that no context owns (a group's, psgpu_group.cpp); its device is current.
+// Free a weld's buffers and events (psgpu_weld.hip), a context's or a group's; its device is current.
 void weld_state_free(WeldState& W);
-// The context's run is finished, superseded by nothing newer, and whole: it can be welded.
+// The context's run is finished, superseded by nothing newer, and whole: it can be welded;
+// ctx_welded: ... and c->weld holds its weld.
 bool weld_run_ready(const psgpu_ctx* c);
-// A group's weld (psgpu_group_weld), host wrappers of the kernels in psgpu_weld.hip.
-// weld_edges: the edge id of every vertex of the context's finished run (all ones: not on an
-// MPU face) into edge[0 .. ctVertices) on the context's device, enqueued on s; the context's
-// device is current.
+inline bool ctx_welded(const psgpu_ctx* c) { return weld_run_ready(c) && c->weld.doneSeq == c->runSeq; }
+// The lattice's edge ids fit their 20 bits a coordinate.
+bool weld_lattice_fits(const uint32_t* dims);
+// The edge id of every vertex of the context's finished run (all ones: not on an MPU face) into
+// edge[0 .. ctVertices) on the context's device, enqueued on s; the context's device is current.
 int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s);
-// weld_gathered: the weld of a gathered mesh of V > 0 vertices whose edge ids are edge[0 .. V),
-// into W's buffers (grown here), enqueued on s of the current device.  ev (null: untimed): five
-// events, one recorded after each launch (mark, resolve, scan, emit, map).  *totals (welded |
-// seam << 32) is written by a copy on s: read it after s has been waited for.
-struct WeldGathered {
+// One weld in three steps (its device current): a context's (psgpu_weld: `records`' vertex records
+// name the edges) or a group's (psgpu_group_weld: the gathered mesh, its edge ids in edge[0 .. V)).
+struct WeldInput {
     const float *pos, *nrm, *col;
     const uint32_t* tris;
-    const uint64_t* edge;
     uint32_t V, T;
+    const uint64_t* edge;
+    const psgpu_ctx* records;
 };
-int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals);
+// W reset (no weld, shells, filter or times) for a mesh of V vertices and T triangles.  False:
+// the mesh is empty, W holds its weld of run `seq` (*info filled) and there is nothing to launch.
+bool weld_begin(WeldState& W, uint32_t V, uint32_t T, uint64_t seq, PsWeldInfo* info);
+// W's buffers grown, then on s six marks: before the table fill, after the mark kernel
+// (k_weld_mark or k_weld_mark_ids), after resolve, scan, emit and map.
+int weld_enqueue(WeldState& W, const WeldInput& in, hipStream_t s, PhaseCursor marks);
+// Waits for s: W holds the weld of run `seq` (*info filled).
+int weld_end(WeldState& W, hipStream_t s, uint64_t seq, PsWeldInfo* info);
 // What psgpu_weld_device / psgpu_download_weld and the group's twins hand out of a finished weld
 // (the callers check that W holds one; for the download its device is current).
 int weld_device(const WeldState& W, PsWeldDevice* out);
@@ -249,7 +249,7 @@ int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32
 void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s);
 // The shells of a weld (psgpu_shells.hip), for a context's weld and a group's alike; the weld's
 // device is current.  shells_run: W holds a finished weld (W.info); blocking on s; `timed`
-// records W.shells.lastMs.  The others serve W.shells once shells_run has succeeded
+// records W.shells.times.  The others serve W.shells once shells_run has succeeded
 // (W.shells.valid).
 int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info);
 int shells_device(const WeldState& W, PsShellsDevice* out);
@@ -257,7 +257,7 @@ int shells_download(const WeldState& W, PsShell* shells, uint32_t capacity, uint
 int shells_times(const WeldState& W, float* ms, int maxPhases, const char** names);
 // The filter of a weld by its shells (psgpu_filter.hip), for a context's weld and a group's
 // alike; the weld's device is current.  filter_run: W holds a finished weld; PARAM_ERROR unless
-// W.shells.valid; blocking on s; `timed` records W.filter.lastMs.  The others serve W.filter once
+// W.shells.valid; blocking on s; `timed` records W.filter.times.  The others serve W.filter once
 // filter_run has succeeded on the current shells (W.filter.valid).
 int filter_run(WeldState& W, hipStream_t s, bool timed, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
                PsFilterInfo* info);

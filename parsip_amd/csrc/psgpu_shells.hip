@@ -6,20 +6,22 @@
 //
 //   k_shells_init       one lane per vertex: parent[v] = v; the largest |coordinate|
 //   k_shells_edges      one lane per triangle: its three edges {lo < hi} enter an
-//                       open-addressing table (64-bit CAS on lo << 32 | hi), then a 64-bit
+//                       open-addressing table (table_claim of lo << 32 | hi), then a 64-bit
 //                       atomic add counts the use (lo->hi: low word, hi->lo: high word)
 //   k_shells_union      one lane per triangle: lock-free union-find, the larger root hooked
 //                       under the smaller by CAS, so a component's root is its smallest vertex
-//   k_shells_flatten    one lane per vertex: its root; roots per block
+//   k_shells_flatten    one lane per vertex: its root; roots per block (block_rank)
 //   k_weld_scan         (psgpu_weld.hip) the block counts scanned; the host reads the shell
 //                       count, the error word and the largest coordinate, sizes the per-shell
 //                       buffers and fixes the scales eA, eV
-//   k_shells_ids        one lane per vertex: a root's shell index (block scan + base), its
+//   k_shells_ids        one lane per vertex: a root's shell index (block_rank + base), its
 //                       accumulator cleared
 //   k_shells_vertices   one lane per vertex: vertexShell; count and bounding box
 //   k_shells_edge_class one lane per table slot: the edge's class into its shell
 //   k_shells_triangles  one lane per triangle: triShell; count and the four integers
 //   k_shells_finish     one lane per shell: its PsShell; the mesh totals
+//
+// table_claim and block_rank are psgpu_mesh_stages.h's, shared with the weld and the filter.
 //
 // The phases are ordered by kernel boundaries alone: no block waits for another inside a
 // launch.  Every loop is bounded; a bound that is hit sets the error word and the call returns
@@ -40,14 +42,11 @@
 #include <cstring>
 
 #include "psgpu_internal.h"
+#include "psgpu_mesh_stages.h"
 
 namespace psgpu {
 
 namespace {
-
-constexpr uint32_t kBlock = 256;
-constexpr uint32_t kWaves = kBlock / 64;
-constexpr uint64_t kEmptyKey = ~0ull;  // no edge: lo < hi < 2^32 leaves it unused
 
 enum : uint32_t { kErrIndex = 1u, kErrTable = 2u, kErrUnion = 4u };  // ShellsCtl::err
 
@@ -83,15 +82,6 @@ struct ShellsParams {
     int eA, eV;
 };
 
-__device__ __forceinline__ uint32_t edge_hash(uint64_t x) {  // murmur3's 64-bit finaliser, as k_weld_mark's
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return (uint32_t)x;
-}
-
 __device__ __forceinline__ uint32_t float_key(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u >> 31) ? ~u : (u | 0x80000000u);
@@ -100,9 +90,9 @@ __device__ __forceinline__ float key_float(uint32_t k) {
     return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_init(ShellsParams q) {
-    __shared__ uint32_t sMax[kWaves];
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_shells_init(ShellsParams q) {
+    __shared__ uint32_t sMax[kMeshWaves];
+    const uint32_t v = blockIdx.x * kMeshBlock + threadIdx.x;
     uint32_t m = 0;
     if (v < q.V) {
         q.parent[v] = v;
@@ -114,7 +104,7 @@ __global__ void __launch_bounds__(kBlock) k_shells_init(ShellsParams q) {
     if ((threadIdx.x & 63u) == 0u) sMax[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kWaves; ++w) m = max(m, sMax[w]);
+        for (uint32_t w = 1; w < kMeshWaves; ++w) m = max(m, sMax[w]);
         if (m) atomicMax(&q.ctl->maxBits, m);
     }
 }
@@ -122,24 +112,15 @@ __global__ void __launch_bounds__(kBlock) k_shells_init(ShellsParams q) {
 // one use of edge x -> y
 __device__ __forceinline__ void edge_use(const ShellsParams& q, uint32_t x, uint32_t y) {
     if (x == y) return;
-    const uint64_t key = (uint64_t)min(x, y) << 32 | max(x, y);
-    uint32_t slot = edge_hash(key) & q.tableMask;
-    // at most half the slots are ever taken (shells_run sizes the table), so an empty or
-    // matching slot comes up; the bound keeps a full table from spinning
-    for (uint32_t tries = 0; tries <= q.tableMask; ++tries) {
-        const uint64_t seen = atomicCAS((unsigned long long*)&q.keys[slot], (unsigned long long)kEmptyKey,
-                                        (unsigned long long)key);
-        if (seen == kEmptyKey || seen == key) {
-            atomicAdd(&q.uses[slot], x < y ? 1ull : 1ull << 32);
-            return;
-        }
-        slot = (slot + 1u) & q.tableMask;
-    }
-    atomicOr(&q.ctl->err, kErrTable);
+    const uint32_t slot = table_claim(q.keys, q.tableMask, (uint64_t)min(x, y) << 32 | max(x, y));
+    if (slot != kNoSlot)
+        atomicAdd(&q.uses[slot], x < y ? 1ull : 1ull << 32);
+    else
+        atomicOr(&q.ctl->err, kErrTable);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_edges(ShellsParams q) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_shells_edges(ShellsParams q) {
+    const uint32_t t = blockIdx.x * kMeshBlock + threadIdx.x;
     if (t >= q.T) return;
     const uint32_t* c = q.tris + (size_t)t * 3u;
     const uint32_t a = c[0], b = c[1], d = c[2];
@@ -184,8 +165,8 @@ __device__ __forceinline__ void shell_union(const ShellsParams& q, uint32_t x, u
     atomicOr(&q.ctl->err, kErrUnion);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_union(ShellsParams q) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_shells_union(ShellsParams q) {
+    const uint32_t t = blockIdx.x * kMeshBlock + threadIdx.x;
     if (t >= q.T) return;
     const uint32_t* c = q.tris + (size_t)t * 3u;
     const uint32_t a = c[0], b = c[1], d = c[2];
@@ -194,23 +175,18 @@ __global__ void __launch_bounds__(kBlock) k_shells_union(ShellsParams q) {
     shell_union(q, b, d);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_flatten(ShellsParams q) {
-    __shared__ uint32_t sRoots[kWaves];
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_shells_flatten(ShellsParams q) {
+    __shared__ uint32_t sRoots[kMeshWaves];
+    const uint32_t v = blockIdx.x * kMeshBlock + threadIdx.x;
     bool root = false;
     if (v < q.V) {
         const uint32_t r = shell_find(q.parent, v);
         q.vertexShell[v] = r;
         root = r == v;
     }
-    const uint32_t n = (uint32_t)__popcll(__ballot(root));
-    if ((threadIdx.x & 63u) == 0u) sRoots[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0;
-        for (uint32_t w = 0; w < kWaves; ++w) a += sRoots[w];
-        q.blockCnt[blockIdx.x] = a;
-    }
+    uint32_t n;
+    (void)block_rank(root, sRoots, &n);
+    if (threadIdx.x == 0) q.blockCnt[blockIdx.x] = n;
 }
 
 __device__ __forceinline__ void acc_clear(ShellAcc* a, uint32_t first) {
@@ -224,16 +200,12 @@ __device__ __forceinline__ void acc_clear(ShellAcc* a, uint32_t first) {
 }
 
 // a root's shell index, left in parent[root]; vertexShell still holds every vertex's root
-__global__ void __launch_bounds__(kBlock) k_shells_ids(ShellsParams q) {
-    __shared__ uint32_t sWave[kWaves];
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_shells_ids(ShellsParams q) {
+    __shared__ uint32_t sWave[kMeshWaves];
+    const uint32_t v = blockIdx.x * kMeshBlock + threadIdx.x;
     const bool root = v < q.V && q.vertexShell[v] == v;
-    const uint64_t b = __ballot(root);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t at = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0u) sWave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    for (uint32_t w = 0; w < wave; ++w) at += sWave[w];
+    uint32_t roots;
+    const uint32_t at = block_rank(root, sWave, &roots);
     if (root) {
         const uint32_t s = (uint32_t)q.blockCnt[blockIdx.x] + at;
         if (s < q.S) {
@@ -375,10 +347,10 @@ __device__ __forceinline__ void block_end(ShellAcc* acc, BlockSums& sh) {
         part_add<K>(acc + sh.shell[threadIdx.x], sh.acc[threadIdx.x]);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_vertices(ShellsParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_shells_vertices(ShellsParams q) {
     __shared__ BlockSums sh;
     block_begin(sh);
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t v = blockIdx.x * kMeshBlock + threadIdx.x;
     bool active = v < q.V;
     uint32_t s = 0;
     ShellAcc p = part_none();
@@ -398,11 +370,11 @@ __global__ void __launch_bounds__(kBlock) k_shells_vertices(ShellsParams q) {
 
 constexpr uint32_t kSlotsPerLane = 8;  // k_shells_edge_class: most slots are empty
 
-__global__ void __launch_bounds__(kBlock) k_shells_edge_class(ShellsParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_shells_edge_class(ShellsParams q) {
     __shared__ BlockSums sh;
     block_begin(sh);
     for (uint32_t it = 0; it < kSlotsPerLane; ++it) {
-        const uint64_t slot = ((uint64_t)blockIdx.x * kSlotsPerLane + it) * kBlock + threadIdx.x;
+        const uint64_t slot = ((uint64_t)blockIdx.x * kSlotsPerLane + it) * kMeshBlock + threadIdx.x;
         bool active = false;
         uint32_t s = 0;
         ShellAcc p = part_none();
@@ -433,10 +405,10 @@ __device__ __forceinline__ void term_split(double x, int e, unsigned long long* 
     *lo = (unsigned long long)(long long)floor((y - h) * 1073741824.0);
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_triangles(ShellsParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_shells_triangles(ShellsParams q) {
     __shared__ BlockSums sh;
     block_begin(sh);
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t t = blockIdx.x * kMeshBlock + threadIdx.x;
     bool active = false;
     uint32_t s = 0;
     ShellAcc p = part_none();
@@ -472,10 +444,10 @@ __host__ __device__ inline double sums_value(unsigned long long hi, unsigned lon
     return (ldexp((double)(long long)hi, -e) + ldexp((double)(long long)lo, -e - 30)) / div;
 }
 
-__global__ void __launch_bounds__(kBlock) k_shells_finish(ShellsParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_shells_finish(ShellsParams q) {
     __shared__ BlockSums sh;
     block_begin(sh);
-    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t s = blockIdx.x * kMeshBlock + threadIdx.x;
     const bool active = s < q.S;
     ShellAcc a = part_none();
     if (active) {
@@ -508,8 +480,6 @@ const char* kShellsPhaseNames[kShellsPhases] = {
     "k_weld_scan",   "k_shells_ids",               "k_shells_vertices",   "k_shells_edge_class", "k_shells_triangles",
     "k_shells_finish"};
 
-inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
@@ -518,7 +488,7 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     S.valid = false;
     W.filter.valid = false;
     memset(&S.info, 0, sizeof(S.info));
-    for (float& ms : S.lastMs) ms = 0.0f;
+    S.times.clear();
     if (V == 0) {  // an empty weld: no shell, nothing to launch
         S.valid = true;
         if (info) *info = S.info;
@@ -528,7 +498,7 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     uint64_t slots = 1024;
     while (slots < 6ull * T) slots <<= 1;
     if (slots > (1ull << 31)) return PSGPU_RET_PARAM_ERROR;
-    const uint32_t blocks = blocks_of(V);
+    const uint32_t blocks = mesh_blocks(V);
     constexpr Growth H = Growth::ByHalf;
     PSGPU_CHECK(S.table.reserve((size_t)slots * 16, H));
     PSGPU_CHECK(S.vertexShell.reserve((size_t)V, H));
@@ -550,12 +520,9 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     q.triShell = S.triShell;
     q.blockCnt = S.blockCnt;
     q.ctl = reinterpret_cast<ShellsCtl*>(S.ctl.ptr);
-    if (timed)
-        for (hipEvent_t& e : S.ev)
-            if (!e) PSGPU_CHECK(hipEventCreate(&e));
-    int phase = 0;
-    auto mark = [&]() -> hipError_t { return timed ? hipEventRecord(S.ev[phase++], s) : hipSuccess; };
-    const dim3 blk(kBlock);
+    PSGPU_CHECK(S.times.begin(timed));
+    auto mark = [&]() { return S.times.mark(s); };
+    const dim3 blk(kMeshBlock);
     PSGPU_CHECK(mark());
     // every key empty (all ones), every use count 0; no error, no coordinate seen
     PSGPU_CHECK(hipMemsetAsync(q.keys, 0xff, (size_t)slots * 8, s));
@@ -563,9 +530,9 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     PSGPU_CHECK(hipMemsetAsync(S.ctl, 0, sizeof(ShellsCtl), s));
     hipLaunchKernelGGL(k_shells_init, dim3(blocks), blk, 0, s, q);
     PSGPU_CHECK(mark());
-    if (T) hipLaunchKernelGGL(k_shells_edges, dim3(blocks_of(T)), blk, 0, s, q);
+    if (T) hipLaunchKernelGGL(k_shells_edges, dim3(mesh_blocks(T)), blk, 0, s, q);
     PSGPU_CHECK(mark());
-    if (T) hipLaunchKernelGGL(k_shells_union, dim3(blocks_of(T)), blk, 0, s, q);
+    if (T) hipLaunchKernelGGL(k_shells_union, dim3(mesh_blocks(T)), blk, 0, s, q);
     PSGPU_CHECK(mark());
     hipLaunchKernelGGL(k_shells_flatten, dim3(blocks), blk, 0, s, q);
     PSGPU_CHECK(mark());
@@ -596,21 +563,18 @@ int shells_run(WeldState& W, hipStream_t s, bool timed, PsShellsInfo* info) {
     PSGPU_CHECK(mark());
     hipLaunchKernelGGL(k_shells_vertices, dim3(blocks), blk, 0, s, q);
     PSGPU_CHECK(mark());
-    hipLaunchKernelGGL(k_shells_edge_class, dim3(blocks_of((slots + kSlotsPerLane - 1) / kSlotsPerLane)), blk, 0, s, q);
+    hipLaunchKernelGGL(k_shells_edge_class, dim3(mesh_blocks((slots + kSlotsPerLane - 1) / kSlotsPerLane)), blk, 0, s, q);
     PSGPU_CHECK(mark());
-    if (T) hipLaunchKernelGGL(k_shells_triangles, dim3(blocks_of(T)), blk, 0, s, q);
+    if (T) hipLaunchKernelGGL(k_shells_triangles, dim3(mesh_blocks(T)), blk, 0, s, q);
     PSGPU_CHECK(mark());
-    hipLaunchKernelGGL(k_shells_finish, dim3(blocks_of(ctShells)), blk, 0, s, q);
+    hipLaunchKernelGGL(k_shells_finish, dim3(mesh_blocks(ctShells)), blk, 0, s, q);
     PSGPU_CHECK(mark());
     PSGPU_CHECK(hipGetLastError());
     ShellsCtl ctl;
     PSGPU_CHECK(hipMemcpyAsync(&ctl, S.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
     PSGPU_CHECK(hipStreamSynchronize(s));
     if (ctl.err) return PSGPU_RET_DEVICE_ERROR;
-    if (timed) {
-        (void)hipEventElapsedTime(&S.lastMs[0], S.ev[0], S.ev[kShellsPhases - 1]);
-        for (int p = 1; p < kShellsPhases; ++p) (void)hipEventElapsedTime(&S.lastMs[p], S.ev[p - 1], S.ev[p]);
-    }
+    S.times.collect();
     const ShellAcc& a = ctl.total;
     PsShellsInfo& o = S.info;
     o.ctShells = ctShells;
@@ -649,29 +613,19 @@ int shells_download(const WeldState& W, PsShell* shells, uint32_t capacity, uint
     if (!S.valid) return PSGPU_RET_PARAM_ERROR;
     const size_t n = S.info.ctShells, V = S.info.ctVertices, T = S.info.ctTriangles;
     if (shells && capacity < n) return PSGPU_RET_PARAM_ERROR;
-    if (shells && n) PSGPU_CHECK(hipMemcpy(shells, S.shells, n * sizeof(PsShell), hipMemcpyDeviceToHost));
-    if (vertexShell && V) PSGPU_CHECK(hipMemcpy(vertexShell, S.vertexShell, V * 4, hipMemcpyDeviceToHost));
-    if (triShell && T) PSGPU_CHECK(hipMemcpy(triShell, S.triShell, T * 4, hipMemcpyDeviceToHost));
+    PSGPU_CHECK(download_if(shells, S.shells, n, sizeof(PsShell)));
+    PSGPU_CHECK(download_if(vertexShell, S.vertexShell, V, 4));
+    PSGPU_CHECK(download_if(triShell, S.triShell, T, 4));
     return PSGPU_RET_SUCCESS;
 }
 
 int shells_times(const WeldState& W, float* ms, int maxPhases, const char** names) {
-    const int n = std::min(maxPhases, kShellsPhases);
-    for (int k = 0; k < n; ++k) {
-        if (ms) ms[k] = W.shells.lastMs[k];
-        if (names) names[k] = kShellsPhaseNames[k];
-    }
-    return n;
+    return W.shells.times.report(ms, maxPhases, names, kShellsPhaseNames);
 }
 
 }  // namespace psgpu
 
 using namespace psgpu;
-
-namespace {
-// the context's current run has been welded (psgpu_weld_device's rule)
-bool ctx_welded(const psgpu_ctx* c) { return weld_run_ready(c) && c->weld.doneSeq == c->runSeq; }
-}  // namespace
 
 extern "C" {
 

@@ -10,25 +10,29 @@
 // Vertices with equal edges are one welded vertex; welded vertices are ordered by their
 // smallest input index and take its attributes; vertexMap[gi] is the welded id.
 //
-//   k_weld_mark     one lane per vertex record: interior records (no off-axis coordinate 0
-//                   or 7) are their own representative; seam records enter an open-addressing
-//                   table (64-bit CAS on the edge id, then a 32-bit atomicMin of gi)
+//   k_weld_mark     one lane per vertex record (record_edge_id): interior records (no off-axis
+//                   coordinate 0 or 7) are their own representative; seam records enter an
+//                   open-addressing table (table_claim of the edge id, then a 32-bit atomicMin
+//                   of gi)
 //   k_weld_resolve  one lane per vertex: representative = the slot's minimum; per-block
 //                   counts of kept and of seam vertices
 //   k_weld_scan     one block: exclusive scan of the block counts, the totals
-//   k_weld_emit     one lane per vertex: the kept vertices' welded ids (block scan + base),
-//                   their pos / nrm / col staged through LDS (16-byte loads, coalesced stores)
+//   k_weld_emit     one lane per vertex: the kept vertices' welded ids (block_rank + base),
+//                   their pos / nrm / col compacted through LDS (compact3: 16-byte loads,
+//                   coalesced stores)
 //   k_weld_map      vertexMap[gi] = id[rep[gi]] and tris = id[rep[tris]], 16 bytes a lane
 //
 // A group's parts (psgpu_group_weld, psgpu_group.cpp) weld in the gathered mesh's global index
 // space.  The gather brings no records, so each part names its vertices' edges itself:
 //
 //   k_weld_edges    on the part's device, one lane per vertex record: edge[gi] = the 62-bit
-//                   edge id k_weld_mark composes (all ones: interior); the arrays are copied
+//                   edge id of record_edge_id (all ones: interior); the arrays are copied
 //                   behind one another on the gathering device
 //   k_weld_mark_ids there, one lane per gathered vertex: k_weld_mark's table insert from the id
 //
-// and k_weld_resolve .. k_weld_map run on the gathered arrays as they do on a context's.
+// and k_weld_resolve .. k_weld_map run on the gathered arrays as they do on a context's:
+// weld_begin / weld_enqueue / weld_end below are the one launch sequence of both.  The stages
+// named in brackets are psgpu_mesh_stages.h's, shared with the shells and the filter.
 //
 // The phases are ordered by kernel boundaries alone: no block waits for another inside a
 // launch.  Every value written is a function of the records alone (the table's slot
@@ -41,30 +45,21 @@
 #include <cstring>
 
 #include "psgpu_internal.h"
+#include "psgpu_mesh_stages.h"
 
 namespace psgpu {
 
 namespace {
 
-constexpr uint32_t kWeldBlock = 256;
-constexpr uint32_t kNoSlot = 0xffffffffu;
-constexpr uint64_t kEmptyKey = ~0ull;  // no edge id: ids use 62 bits
-constexpr uint32_t kCoordBits = 20;    // per lattice coordinate of the edge id (psgpu_weld checks the lattice)
-
 struct WeldParams {
-    const VertexKey* vk;
-    const uint64_t* offs;
-    uint32_t vShardCap;
-    uint32_t shardV[kShards];  // vertex records per shard (the run's host counters)
-    uint32_t dims[3];
-    uint32_t mpuBegin, mpuCount;
+    WeldRecords rec;     // k_weld_mark
     uint32_t V, T;
     uint64_t* keys;      // table: tableMask + 1 edge ids ...
     uint32_t* mins;      // ... and the smallest gi seen with each
     uint32_t tableMask;
-    uint32_t* rep;       // V: k_weld_mark the table slot (kNoSlot: interior), k_weld_resolve the representative
+    uint32_t* rep;       // V: the mark kernel the table slot (kNoSlot: interior), k_weld_resolve the representative
     uint32_t* kid;       // V: welded id of a kept vertex
-    uint64_t* blockCnt;  // blocks + 1: kept | seam << 32 per block of kWeldBlock vertices, then scanned; [blocks] the totals
+    uint64_t* blockCnt;  // blocks + 1: kept | seam << 32 per block of kMeshBlock vertices, then scanned; [blocks] the totals
     uint32_t blocks;
     const float *pos, *nrm, *col;
     const uint32_t* tris;
@@ -74,146 +69,39 @@ struct WeldParams {
     uint32_t mapBlocks;  // k_weld_map: blocks [0, mapBlocks) write the map, the rest the triangles
 };
 
-__device__ __forceinline__ uint32_t weld_hash(uint64_t x) {  // murmur3's 64-bit finaliser
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return (uint32_t)x;
+// vertex gi on edge `id` (kEmptyKey: interior) enters the table: rep[gi] = its slot
+__device__ __forceinline__ void weld_insert(const WeldParams& q, uint32_t gi, uint64_t id) {
+    const uint32_t slot = id == kEmptyKey ? kNoSlot : table_claim(q.keys, q.tableMask, id);
+    if (slot != kNoSlot) atomicMin(&q.mins[slot], gi);
+    q.rep[gi] = slot;
 }
 
-__global__ void __launch_bounds__(kWeldBlock) k_weld_mark(WeldParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_weld_mark(WeldParams q) {
     __shared__ uint32_t sStart[kShards + 1];
-    if (threadIdx.x == 0) {
-        uint32_t at = 0;
-        for (int k = 0; k < kShards; ++k) {
-            sStart[k] = at;
-            at += q.shardV[k];
-        }
-        sStart[kShards] = at;
-    }
-    __syncthreads();
-    const uint32_t r = blockIdx.x * kWeldBlock + threadIdx.x;
-    if (r >= sStart[kShards]) return;
-    uint32_t shard = 0;  // the last shard whose first record is <= r
-    for (uint32_t step = kShards / 2; step; step >>= 1)
-        if (sStart[shard + step] <= r) shard += step;
-    const VertexKey K = q.vk[(size_t)shard * q.vShardCap + (r - sStart[shard])];
-    if (K.w >= q.mpuCount) return;
-    const uint32_t gi = (uint32_t)q.offs[K.w] + (K.vidKey & 0xffffu);
-    if (gi >= q.V) return;
-    const uint32_t key = K.vidKey >> 16;
-    const uint32_t sx = key & 7u, sy = (key >> 3) & 7u, sz = (key >> 6) & 7u, ax = (key >> 9) & 3u;
-    // on an MPU face: an off-axis coordinate on the MPU's first or last corner plane
-    const bool fx = sx == 0u || sx == 7u, fy = sy == 0u || sy == 7u, fz = sz == 0u || sz == 7u;
-    const bool seam = (ax != 0u && fx) || (ax != 1u && fy) || (ax != 2u && fz);
-    if (!seam) {
-        q.rep[gi] = kNoSlot;
-        return;
-    }
-    const uint32_t m = K.w + q.mpuBegin;
-    const uint32_t nyz = q.dims[1] * q.dims[2];
-    const uint32_t i = m / nyz, jk = m - i * nyz;
-    const uint32_t j = jk / q.dims[2], k = jk - j * q.dims[2];
-    const uint64_t id = ((((uint64_t)(7u * i + sx) << kCoordBits | (uint64_t)(7u * j + sy)) << kCoordBits |
-                          (uint64_t)(7u * k + sz)) << 2) | ax;
-    uint32_t slot = weld_hash(id) & q.tableMask;
-    // at most half the slots are ever taken (psgpu_weld sizes the table), so an empty or
-    // matching slot comes up; the bound only keeps a corrupt record from spinning
-    for (uint32_t tries = 0; tries <= q.tableMask; ++tries) {
-        const uint64_t seen = atomicCAS((unsigned long long*)&q.keys[slot], (unsigned long long)kEmptyKey,
-                                        (unsigned long long)id);
-        if (seen == kEmptyKey || seen == id) {
-            atomicMin(&q.mins[slot], gi);
-            q.rep[gi] = slot;
-            return;
-        }
-        slot = (slot + 1u) & q.tableMask;
-    }
-    q.rep[gi] = kNoSlot;
+    uint32_t gi;
+    const uint64_t id = record_edge_id(q.rec, q.V, sStart, &gi);
+    if (gi != kNoSlot) weld_insert(q, gi, id);
 }
 
-// A part's records as edge ids (psgpu_group_weld): k_weld_mark's shard lookup, seam test and
-// id, written to edge[gi] (gi local to the part) instead of entering a table; the array was
-// filled with ones, so an interior record and a missing one both read as kEmptyKey.
-struct WeldEdgeParams {
-    const VertexKey* vk;
-    const uint64_t* offs;
-    uint32_t vShardCap;
-    uint32_t shardV[kShards];
-    uint32_t dims[3];
-    uint32_t mpuBegin, mpuCount;
-    uint32_t V;
-    uint64_t* edge;  // V
-};
-
-__global__ void __launch_bounds__(kWeldBlock) k_weld_edges(WeldEdgeParams q) {
+// A part's records as edge ids (psgpu_group_weld): edge[gi] (gi local to the part) instead of
+// a table; the array was filled with ones, so an interior record and a missing one both read
+// as kEmptyKey.
+__global__ void __launch_bounds__(kMeshBlock) k_weld_edges(WeldRecords q, uint32_t V, uint64_t* edge) {
     __shared__ uint32_t sStart[kShards + 1];
-    if (threadIdx.x == 0) {
-        uint32_t at = 0;
-        for (int k = 0; k < kShards; ++k) {
-            sStart[k] = at;
-            at += q.shardV[k];
-        }
-        sStart[kShards] = at;
-    }
-    __syncthreads();
-    const uint32_t r = blockIdx.x * kWeldBlock + threadIdx.x;
-    if (r >= sStart[kShards]) return;
-    uint32_t shard = 0;
-    for (uint32_t step = kShards / 2; step; step >>= 1)
-        if (sStart[shard + step] <= r) shard += step;
-    const VertexKey K = q.vk[(size_t)shard * q.vShardCap + (r - sStart[shard])];
-    if (K.w >= q.mpuCount) return;
-    const uint32_t gi = (uint32_t)q.offs[K.w] + (K.vidKey & 0xffffu);
-    if (gi >= q.V) return;
-    const uint32_t key = K.vidKey >> 16;
-    const uint32_t sx = key & 7u, sy = (key >> 3) & 7u, sz = (key >> 6) & 7u, ax = (key >> 9) & 3u;
-    const bool fx = sx == 0u || sx == 7u, fy = sy == 0u || sy == 7u, fz = sz == 0u || sz == 7u;
-    if (!((ax != 0u && fx) || (ax != 1u && fy) || (ax != 2u && fz))) return;  // interior: stays kEmptyKey
-    const uint32_t m = K.w + q.mpuBegin;
-    const uint32_t nyz = q.dims[1] * q.dims[2];
-    const uint32_t i = m / nyz, jk = m - i * nyz;
-    const uint32_t j = jk / q.dims[2], k = jk - j * q.dims[2];
-    q.edge[gi] = ((((uint64_t)(7u * i + sx) << kCoordBits | (uint64_t)(7u * j + sy)) << kCoordBits |
-                   (uint64_t)(7u * k + sz)) << 2) | ax;
+    uint32_t gi;
+    const uint64_t id = record_edge_id(q, V, sStart, &gi);
+    if (id != kEmptyKey) edge[gi] = id;
 }
 
 // k_weld_mark over the gathered vertices' edge ids: one lane per vertex, the same insert
-__global__ void __launch_bounds__(kWeldBlock) k_weld_mark_ids(WeldParams q, const uint64_t* __restrict__ edge) {
-    const uint32_t gi = blockIdx.x * kWeldBlock + threadIdx.x;
-    if (gi >= q.V) return;
-    const uint64_t id = edge[gi];
-    if (id == kEmptyKey) {
-        q.rep[gi] = kNoSlot;
-        return;
-    }
-    uint32_t slot = weld_hash(id) & q.tableMask;
-    for (uint32_t tries = 0; tries <= q.tableMask; ++tries) {
-        const uint64_t seen = atomicCAS((unsigned long long*)&q.keys[slot], (unsigned long long)kEmptyKey,
-                                        (unsigned long long)id);
-        if (seen == kEmptyKey || seen == id) {
-            atomicMin(&q.mins[slot], gi);
-            q.rep[gi] = slot;
-            return;
-        }
-        slot = (slot + 1u) & q.tableMask;
-    }
-    q.rep[gi] = kNoSlot;
+__global__ void __launch_bounds__(kMeshBlock) k_weld_mark_ids(WeldParams q, const uint64_t* __restrict__ edge) {
+    const uint32_t gi = blockIdx.x * kMeshBlock + threadIdx.x;
+    if (gi < q.V) weld_insert(q, gi, edge[gi]);
 }
 
-// lanes of the wave below this one with the flag set; *total: lanes of the wave with it
-__device__ __forceinline__ uint32_t wave_excl_count(bool flag, uint32_t* total) {
-    const uint64_t b = __ballot(flag);
-    const uint32_t lane = threadIdx.x & 63u;
-    *total = (uint32_t)__popcll(b);
-    return (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-}
-
-__global__ void __launch_bounds__(kWeldBlock) k_weld_resolve(WeldParams q) {
-    __shared__ uint32_t sKept[kWeldBlock / 64], sSeam[kWeldBlock / 64];
-    const uint32_t gi = blockIdx.x * kWeldBlock + threadIdx.x;
+__global__ void __launch_bounds__(kMeshBlock) k_weld_resolve(WeldParams q) {
+    __shared__ uint32_t sKept[kMeshWaves], sSeam[kMeshWaves];
+    const uint32_t gi = blockIdx.x * kMeshBlock + threadIdx.x;
     bool kept = false, seam = false;
     if (gi < q.V) {
         const uint32_t slot = q.rep[gi];
@@ -223,35 +111,26 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_resolve(WeldParams q) {
         q.rep[gi] = rep;
         kept = rep == gi;
     }
-    uint32_t nk, ns;
-    (void)wave_excl_count(kept, &nk);
-    (void)wave_excl_count(seam, &ns);
-    if ((threadIdx.x & 63u) == 0u) {
-        sKept[threadIdx.x >> 6] = nk;
-        sSeam[threadIdx.x >> 6] = ns;
-    }
+    const uint32_t ak = wave_rank(kept, sKept), as = wave_rank(seam, sSeam);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0;
-        for (uint32_t w = 0; w < kWeldBlock / 64; ++w) {
-            a += sKept[w];
-            b += sSeam[w];
-        }
-        q.blockCnt[blockIdx.x] = (uint64_t)a | (uint64_t)b << 32;
-    }
+    uint32_t nk, ns;
+    (void)block_rank_sum(ak, sKept, &nk);
+    (void)block_rank_sum(as, sSeam, &ns);
+    if (threadIdx.x == 0) q.blockCnt[blockIdx.x] = (uint64_t)nk | (uint64_t)ns << 32;
 }
 
 // one block: blockCnt[0..blocks) becomes its exclusive scan, blockCnt[blocks] the totals
-// (both halves of a word stay below 2^32: they count vertices)
-__global__ void __launch_bounds__(kWeldBlock) k_weld_scan(WeldParams q) {
-    __shared__ uint64_t sWave[kWeldBlock / 64];
+// (both halves of a word stay below 2^32: they count vertices); also the shells' and the
+// filter's scan (weld_scan_blocks)
+__global__ void __launch_bounds__(kMeshBlock) k_weld_scan(uint64_t* blockCnt, uint32_t blocks) {
+    __shared__ uint64_t sWave[kMeshWaves];
     __shared__ uint64_t sCarry;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) sCarry = 0;
     __syncthreads();
-    for (uint32_t base = 0; base < q.blocks; base += kWeldBlock) {
+    for (uint32_t base = 0; base < blocks; base += kMeshBlock) {
         const uint32_t b = base + threadIdx.x;
-        const uint64_t v = b < q.blocks ? q.blockCnt[b] : 0ull;
+        const uint64_t v = b < blocks ? blockCnt[b] : 0ull;
         uint64_t incl = v;
         for (uint32_t d = 1; d < 64; d <<= 1) {
             const uint64_t up = __shfl_up(incl, d, 64);
@@ -261,62 +140,29 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_scan(WeldParams q) {
         __syncthreads();
         uint64_t before = sCarry;
         for (uint32_t w = 0; w < wave; ++w) before += sWave[w];
-        if (b < q.blocks) q.blockCnt[b] = before + incl - v;
+        if (b < blocks) blockCnt[b] = before + incl - v;
         __syncthreads();
-        if (threadIdx.x == kWeldBlock - 1) sCarry = before + incl;
+        if (threadIdx.x == kMeshBlock - 1) sCarry = before + incl;
         __syncthreads();
     }
-    if (threadIdx.x == 0) q.blockCnt[q.blocks] = sCarry;
+    if (threadIdx.x == 0) blockCnt[blocks] = sCarry;
 }
 
-// one attribute array of the block's vertices [v0, v0 + n): 16-byte loads into LDS, the kept
-// ones compacted in LDS, then stored as consecutive words from welded vertex `base`
-__device__ __forceinline__ void weld_copy(const float* __restrict__ src, float* __restrict__ dst, uint32_t v0,
-                                          uint32_t n, bool kept, uint32_t at, uint32_t nKept, uint32_t base,
-                                          float* sIn, float* sOut) {
-    const uint32_t words = 3u * n;
-    const float* s = src + (size_t)v0 * 3u;  // v0 is a multiple of kWeldBlock: 16-byte aligned
-    for (uint32_t x = threadIdx.x * 4u; x < words; x += kWeldBlock * 4u) {
-        if (x + 4u <= words) {
-            *reinterpret_cast<float4*>(sIn + x) = *reinterpret_cast<const float4*>(s + x);
-        } else {
-            for (uint32_t y = x; y < words; ++y) sIn[y] = s[y];
-        }
-    }
-    __syncthreads();
-    if (kept) {
-        sOut[3u * at] = sIn[3u * threadIdx.x];
-        sOut[3u * at + 1u] = sIn[3u * threadIdx.x + 1u];
-        sOut[3u * at + 2u] = sIn[3u * threadIdx.x + 2u];
-    }
-    __syncthreads();
-    float* d = dst + (size_t)base * 3u;
-    for (uint32_t x = threadIdx.x; x < 3u * nKept; x += kWeldBlock) d[x] = sOut[x];
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(kWeldBlock) k_weld_emit(WeldParams q) {
-    __shared__ __attribute__((aligned(16))) float sIn[3 * kWeldBlock];
-    __shared__ float sOut[3 * kWeldBlock];
-    __shared__ uint32_t sWave[kWeldBlock / 64];
-    const uint32_t v0 = blockIdx.x * kWeldBlock;
+__global__ void __launch_bounds__(kMeshBlock) k_weld_emit(WeldParams q) {
+    __shared__ __attribute__((aligned(16))) uint32_t sIn[3 * kMeshBlock];
+    __shared__ uint32_t sOut[3 * kMeshBlock];
+    __shared__ uint32_t sWave[kMeshWaves];
+    const uint32_t v0 = blockIdx.x * kMeshBlock;
     const uint32_t gi = v0 + threadIdx.x;
-    const uint32_t n = min(kWeldBlock, q.V - v0);
+    const uint32_t n = min(kMeshBlock, q.V - v0);
     const bool kept = gi < q.V && q.rep[gi] == gi;
-    uint32_t nk;
-    uint32_t at = wave_excl_count(kept, &nk);
-    if ((threadIdx.x & 63u) == 0u) sWave[threadIdx.x >> 6] = nk;
-    __syncthreads();
-    uint32_t nKept = 0;
-    for (uint32_t w = 0; w < kWeldBlock / 64; ++w) {
-        if (w < (threadIdx.x >> 6)) at += sWave[w];
-        nKept += sWave[w];
-    }
+    uint32_t nKept;
+    const uint32_t at = block_rank(kept, sWave, &nKept);
     const uint32_t base = (uint32_t)q.blockCnt[blockIdx.x];
     if (kept) q.kid[gi] = base + at;
-    weld_copy(q.pos, q.wpos, v0, n, kept, at, nKept, base, sIn, sOut);
-    weld_copy(q.nrm, q.wnrm, v0, n, kept, at, nKept, base, sIn, sOut);
-    weld_copy(q.col, q.wcol, v0, n, kept, at, nKept, base, sIn, sOut);
+    compact3(q.pos, q.wpos, v0, n, kept, at, nKept, base, sIn, sOut);
+    compact3(q.nrm, q.wnrm, v0, n, kept, at, nKept, base, sIn, sOut);
+    compact3(q.col, q.wcol, v0, n, kept, at, nKept, base, sIn, sOut);
 }
 
 __device__ __forceinline__ uint32_t weld_id(const WeldParams& q, uint32_t v) {
@@ -326,9 +172,9 @@ __device__ __forceinline__ uint4 weld_id4(const WeldParams& q, uint4 v) {
     return make_uint4(weld_id(q, v.x), weld_id(q, v.y), weld_id(q, v.z), weld_id(q, v.w));
 }
 
-__global__ void __launch_bounds__(kWeldBlock) k_weld_map(WeldParams q) {
+__global__ void __launch_bounds__(kMeshBlock) k_weld_map(WeldParams q) {
     if (blockIdx.x < q.mapBlocks) {  // vertexMap: 4 vertices a lane
-        const uint32_t x = (blockIdx.x * kWeldBlock + threadIdx.x) * 4u;
+        const uint32_t x = (blockIdx.x * kMeshBlock + threadIdx.x) * 4u;
         if (x + 4u <= q.V) {
             const uint4 r = *reinterpret_cast<const uint4*>(q.rep + x);
             *reinterpret_cast<uint4*>(q.map + x) = make_uint4(q.kid[r.x], q.kid[r.y], q.kid[r.z], q.kid[r.w]);
@@ -339,7 +185,7 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_map(WeldParams q) {
     }
     // triangles: 4 a lane (12 indices, three 16-byte words)
     const uint64_t words = 3ull * q.T;
-    const uint64_t x = ((uint64_t)(blockIdx.x - q.mapBlocks) * kWeldBlock + threadIdx.x) * 12ull;
+    const uint64_t x = ((uint64_t)(blockIdx.x - q.mapBlocks) * kMeshBlock + threadIdx.x) * 12ull;
     if (x + 12ull <= words) {
         const uint4* s = reinterpret_cast<const uint4*>(q.tris + x);
         uint4* d = reinterpret_cast<uint4*>(q.wtris + x);
@@ -355,15 +201,21 @@ __global__ void __launch_bounds__(kWeldBlock) k_weld_map(WeldParams q) {
 const char* kWeldPhaseNames[kWeldPhases] = {"weld total", "table fill + k_weld_mark", "k_weld_resolve", "k_weld_scan",
                                             "k_weld_emit", "k_weld_map"};
 
-// the run's vertex records per shard (its host counters): one record per vertex, every shard
-// within its capacity (finish re-runs until they fit)
-int weld_shard_counts(const psgpu_ctx* c, uint32_t V, uint32_t* shardV) {
+// The run's vertex records: one per vertex, every shard within its capacity (finish re-runs
+// until they fit); shardV from the run's host counters.
+int weld_records(const psgpu_ctx* c, uint32_t V, WeldRecords& r) {
     uint64_t recs = 0;
     for (int k = 0; k < kShards; ++k) {
-        shardV[k] = c->hostCtr->shard[k].v;
-        if (shardV[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;
-        recs += shardV[k];
+        r.shardV[k] = c->hostCtr->shard[k].v;
+        if (r.shardV[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;
+        recs += r.shardV[k];
     }
+    r.vk = c->vk;
+    r.offs = c->offs;
+    r.vShardCap = c->vShardCap;
+    for (int a = 0; a < 3; ++a) r.dims[a] = c->dims[a];
+    r.mpuBegin = c->mpuBegin;
+    r.mpuCount = c->mpuCount;
     return recs == V ? PSGPU_RET_SUCCESS : PSGPU_RET_DEVICE_ERROR;
 }
 
@@ -373,7 +225,7 @@ int weld_prepare(WeldState& W, uint32_t V, uint32_t T, WeldParams& q, uint32_t* 
     // at most V seam records: a table of >= 2 V slots stays at most half full
     uint32_t slots = 1024;
     while (slots < 2ull * V && slots < (1u << 31)) slots <<= 1;
-    const uint32_t blocks = (V + kWeldBlock - 1) / kWeldBlock;
+    const uint32_t blocks = mesh_blocks(V);
     constexpr Growth H = Growth::ByHalf;
     PSGPU_CHECK(W.table.reserve((size_t)slots * 12, H));
     PSGPU_CHECK(W.rep.reserve((size_t)V + 4, H));
@@ -398,24 +250,8 @@ int weld_prepare(WeldState& W, uint32_t V, uint32_t T, WeldParams& q, uint32_t* 
     q.wcol = W.col;
     q.wtris = W.tris;
     q.map = W.map;
-    q.mapBlocks = (V + 4u * kWeldBlock - 1u) / (4u * kWeldBlock);
+    q.mapBlocks = (V + 4u * kMeshBlock - 1u) / (4u * kMeshBlock);
     *slotsOut = slots;
-    return PSGPU_RET_SUCCESS;
-}
-
-// The launches after the mark, shared by psgpu_weld and a group's weld; ev (null: untimed): four
-// events, one recorded after each launch.
-int weld_after_mark(const WeldParams& q, hipStream_t s, hipEvent_t* ev) {
-    const uint32_t triBlocks = (uint32_t)(((uint64_t)q.T + 4ull * kWeldBlock - 1ull) / (4ull * kWeldBlock));
-    hipLaunchKernelGGL(k_weld_resolve, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
-    if (ev) PSGPU_CHECK(hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kWeldBlock), 0, s, q);
-    if (ev) PSGPU_CHECK(hipEventRecord(ev[1], s));
-    hipLaunchKernelGGL(k_weld_emit, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
-    if (ev) PSGPU_CHECK(hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(k_weld_map, dim3(q.mapBlocks + triBlocks), dim3(kWeldBlock), 0, s, q);
-    if (ev) PSGPU_CHECK(hipEventRecord(ev[3], s));
-    PSGPU_CHECK(hipGetLastError());
     return PSGPU_RET_SUCCESS;
 }
 
@@ -426,43 +262,31 @@ bool weld_run_ready(const psgpu_ctx* c) {
     return c && !c->pending && c->haveResult && c->finishedSeq == c->runSeq;
 }
 
+bool weld_lattice_fits(const uint32_t* dims) {
+    for (int a = 0; a < 3; ++a)
+        if (7ull * dims[a] >= (1ull << kCoordBits)) return false;
+    return true;
+}
+
 void weld_state_free(WeldState& W) {
-    for (hipEvent_t e : W.filter.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : W.shells.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : W.ev)
-        if (e) (void)hipEventDestroy(e);
+    W.filter.times.free();
+    W.shells.times.free();
+    W.times.free();
     W = WeldState{};  // releases the weld's buffers, the shells' and the filter's
 }
 
-void weld_free(psgpu_ctx* c) { weld_state_free(c->weld); }
-
 void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s) {
-    WeldParams q;
-    memset(&q, 0, sizeof(q));
-    q.blockCnt = blockCnt;
-    q.blocks = blocks;
-    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kWeldBlock), 0, s, q);
+    hipLaunchKernelGGL(k_weld_scan, dim3(1), dim3(kMeshBlock), 0, s, blockCnt, blocks);
 }
 
 int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s) {
     const uint32_t V = c->info.ctVertices;
     if (V == 0) return PSGPU_RET_SUCCESS;
-    WeldEdgeParams q;
-    memset(&q, 0, sizeof(q));
-    const int rc = weld_shard_counts(c, V, q.shardV);
+    WeldRecords r;
+    const int rc = weld_records(c, V, r);
     if (rc != PSGPU_RET_SUCCESS) return rc;
-    q.vk = c->vk;
-    q.offs = c->offs;
-    q.vShardCap = c->vShardCap;
-    for (int a = 0; a < 3; ++a) q.dims[a] = c->dims[a];
-    q.mpuBegin = c->mpuBegin;
-    q.mpuCount = c->mpuCount;
-    q.V = V;
-    q.edge = edge;
     PSGPU_CHECK(hipMemsetAsync(edge, 0xff, (size_t)V * 8, s));
-    hipLaunchKernelGGL(k_weld_edges, dim3((V + kWeldBlock - 1) / kWeldBlock), dim3(kWeldBlock), 0, s, q);
+    hipLaunchKernelGGL(k_weld_edges, dim3(mesh_blocks(V)), dim3(kMeshBlock), 0, s, r, V, edge);
     PSGPU_CHECK(hipGetLastError());
     return PSGPU_RET_SUCCESS;
 }
@@ -478,30 +302,71 @@ int weld_device(const WeldState& W, PsWeldDevice* out) {
 
 int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap) {
     const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
-    if (pos && V) PSGPU_CHECK(hipMemcpy(pos, W.pos, V * 12, hipMemcpyDeviceToHost));
-    if (nrm && V) PSGPU_CHECK(hipMemcpy(nrm, W.nrm, V * 12, hipMemcpyDeviceToHost));
-    if (col && V) PSGPU_CHECK(hipMemcpy(col, W.col, V * 12, hipMemcpyDeviceToHost));
-    if (tris && T) PSGPU_CHECK(hipMemcpy(tris, W.tris, T * 12, hipMemcpyDeviceToHost));
-    if (vertexMap && Vin) PSGPU_CHECK(hipMemcpy(vertexMap, W.map, Vin * 4, hipMemcpyDeviceToHost));
+    PSGPU_CHECK(download_if(pos, W.pos, V, 12));
+    PSGPU_CHECK(download_if(nrm, W.nrm, V, 12));
+    PSGPU_CHECK(download_if(col, W.col, V, 12));
+    PSGPU_CHECK(download_if(tris, W.tris, T, 12));
+    PSGPU_CHECK(download_if(vertexMap, W.map, Vin, 4));
     return PSGPU_RET_SUCCESS;
 }
 
-int weld_gathered(WeldState& W, const WeldGathered& in, hipStream_t s, hipEvent_t* ev, uint64_t* totals) {
+bool weld_begin(WeldState& W, uint32_t V, uint32_t T, uint64_t seq, PsWeldInfo* info) {
+    W.doneSeq = ~0ull;
+    W.shells.valid = false;
+    W.filter.valid = false;
+    memset(&W.info, 0, sizeof(W.info));
+    W.info.ctInputVertices = V;
+    W.info.ctTriangles = T;
+    W.times.clear();
+    if (V) return true;
+    W.doneSeq = seq;  // an empty mesh welds to an empty mesh
+    if (info) *info = W.info;
+    return false;
+}
+
+int weld_enqueue(WeldState& W, const WeldInput& in, hipStream_t s, PhaseCursor marks) {
     WeldParams q;
     memset(&q, 0, sizeof(q));
+    int rc = in.records ? weld_records(in.records, in.V, q.rec) : PSGPU_RET_SUCCESS;
+    if (rc != PSGPU_RET_SUCCESS) return rc;
     uint32_t slots = 0;
-    const int rc = weld_prepare(W, in.V, in.T, q, &slots);
+    rc = weld_prepare(W, in.V, in.T, q, &slots);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     q.pos = in.pos;
     q.nrm = in.nrm;
     q.col = in.col;
     q.tris = in.tris;
+    const dim3 blk(kMeshBlock);
+    const uint32_t triBlocks = mesh_blocks(((uint64_t)q.T + 3u) / 4u);  // k_weld_map: 4 triangles a lane
+    PSGPU_CHECK(marks.mark(s));
+    // every key empty (all ones), every minimum 0xffffffff
     PSGPU_CHECK(hipMemsetAsync(W.table, 0xff, (size_t)slots * 12, s));
-    hipLaunchKernelGGL(k_weld_mark_ids, dim3(q.blocks), dim3(kWeldBlock), 0, s, q, in.edge);
-    if (ev) PSGPU_CHECK(hipEventRecord(ev[0], s));
-    const int rt = weld_after_mark(q, s, ev ? ev + 1 : nullptr);
-    if (rt != PSGPU_RET_SUCCESS) return rt;
-    PSGPU_CHECK(hipMemcpyAsync(totals, W.blockCnt + q.blocks, sizeof(*totals), hipMemcpyDeviceToHost, s));
+    if (in.records)
+        hipLaunchKernelGGL(k_weld_mark, dim3(q.blocks), blk, 0, s, q);
+    else
+        hipLaunchKernelGGL(k_weld_mark_ids, dim3(q.blocks), blk, 0, s, q, in.edge);
+    PSGPU_CHECK(marks.mark(s));
+    hipLaunchKernelGGL(k_weld_resolve, dim3(q.blocks), blk, 0, s, q);
+    PSGPU_CHECK(marks.mark(s));
+    hipLaunchKernelGGL(k_weld_scan, dim3(1), blk, 0, s, q.blockCnt, q.blocks);
+    PSGPU_CHECK(marks.mark(s));
+    hipLaunchKernelGGL(k_weld_emit, dim3(q.blocks), blk, 0, s, q);
+    PSGPU_CHECK(marks.mark(s));
+    hipLaunchKernelGGL(k_weld_map, dim3(q.mapBlocks + triBlocks), blk, 0, s, q);
+    PSGPU_CHECK(marks.mark(s));
+    PSGPU_CHECK(hipGetLastError());
+    return PSGPU_RET_SUCCESS;
+}
+
+int weld_end(WeldState& W, hipStream_t s, uint64_t seq, PsWeldInfo* info) {
+    uint64_t totals = 0;  // welded | seam << 32, behind the scanned block counts
+    PSGPU_CHECK(hipMemcpyAsync(&totals, W.blockCnt + mesh_blocks(W.info.ctInputVertices), sizeof(totals),
+                               hipMemcpyDeviceToHost, s));
+    PSGPU_CHECK(hipStreamSynchronize(s));
+    W.info.ctVertices = (uint32_t)totals;
+    W.info.ctSeamVertices = (uint32_t)(totals >> 32);
+    W.doneSeq = seq;
+    if (info) *info = W.info;
     return PSGPU_RET_SUCCESS;
 }
 
@@ -514,87 +379,33 @@ extern "C" {
 int psgpu_weld(psgpu_ctx* c, PsWeldInfo* info) {
     if (!weld_run_ready(c)) return PSGPU_RET_PARAM_ERROR;
     if (c->info.firstOverflowMPU >= 0) return PSGPU_RET_PARAM_ERROR;  // past the reference's 512 per MPU (records complete)
-    for (int a = 0; a < 3; ++a)
-        if (7ull * c->dims[a] >= (1ull << kCoordBits)) return PSGPU_RET_PARAM_ERROR;
+    if (!weld_lattice_fits(c->dims)) return PSGPU_RET_PARAM_ERROR;
     int rc = set_device(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     WeldState& W = c->weld;
-    const uint32_t V = c->info.ctVertices, T = c->info.ctTriangles;
-    W.doneSeq = ~0ull;
-    W.shells.valid = false;
-    W.filter.valid = false;
-    memset(&W.info, 0, sizeof(W.info));
-    W.info.ctInputVertices = V;
-    W.info.ctTriangles = T;
-    for (float& ms : W.lastMs) ms = 0.0f;
-    if (V == 0) {  // nothing to launch: an empty mesh welds to an empty mesh
-        W.doneSeq = c->runSeq;
-        if (info) *info = W.info;
-        return PSGPU_RET_SUCCESS;
-    }
-    WeldParams q;
-    memset(&q, 0, sizeof(q));
-    rc = weld_shard_counts(c, V, q.shardV);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    uint32_t slots = 0;
-    rc = weld_prepare(W, V, T, q, &slots);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    q.vk = c->vk;
-    q.offs = c->offs;
-    q.vShardCap = c->vShardCap;
-    for (int a = 0; a < 3; ++a) q.dims[a] = c->dims[a];
-    q.mpuBegin = c->mpuBegin;
-    q.mpuCount = c->mpuCount;
-    q.pos = c->pos;
-    q.nrm = c->nrm;
-    q.col = c->col;
-    q.tris = c->tris;
-    hipStream_t s = c->stream;
-    const bool timed = c->timing != 0;
-    if (timed)
-        for (hipEvent_t& e : W.ev)
-            if (!e) PSGPU_CHECK(hipEventCreate(&e));
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[0], s));
-    // every key empty (all ones), every minimum 0xffffffff
-    PSGPU_CHECK(hipMemsetAsync(W.table, 0xff, (size_t)slots * 12, s));
-    hipLaunchKernelGGL(k_weld_mark, dim3(q.blocks), dim3(kWeldBlock), 0, s, q);
-    if (timed) PSGPU_CHECK(hipEventRecord(W.ev[1], s));
-    rc = weld_after_mark(q, s, timed ? W.ev + 2 : nullptr);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    uint64_t totals = 0;
-    PSGPU_CHECK(hipMemcpyAsync(&totals, W.blockCnt + q.blocks, sizeof(totals), hipMemcpyDeviceToHost, s));
-    PSGPU_CHECK(hipStreamSynchronize(s));
-    if (timed) {
-        (void)hipEventElapsedTime(&W.lastMs[0], W.ev[0], W.ev[kWeldPhases - 1]);
-        for (int k = 1; k < kWeldPhases; ++k) (void)hipEventElapsedTime(&W.lastMs[k], W.ev[k - 1], W.ev[k]);
-    }
-    W.info.ctVertices = (uint32_t)totals;
-    W.info.ctSeamVertices = (uint32_t)(totals >> 32);
-    W.doneSeq = c->runSeq;
-    if (info) *info = W.info;
-    return PSGPU_RET_SUCCESS;
+    const WeldInput in{c->pos, c->nrm, c->col, c->tris, c->info.ctVertices, c->info.ctTriangles, nullptr, c};
+    if (!weld_begin(W, in.V, in.T, c->runSeq, info)) return PSGPU_RET_SUCCESS;
+    PSGPU_CHECK(W.times.begin(c->timing != 0));
+    rc = weld_enqueue(W, in, c->stream, W.times.rest());
+    if (rc == PSGPU_RET_SUCCESS) rc = weld_end(W, c->stream, c->runSeq, info);
+    if (rc == PSGPU_RET_SUCCESS) W.times.collect();
+    return rc;
 }
 
 int psgpu_weld_device(psgpu_ctx* c, PsWeldDevice* out) {
-    if (!out || !weld_run_ready(c) || c->weld.doneSeq != c->runSeq) return PSGPU_RET_PARAM_ERROR;
+    if (!out || !ctx_welded(c)) return PSGPU_RET_PARAM_ERROR;
     return weld_device(c->weld, out);
 }
 
 int psgpu_download_weld(psgpu_ctx* c, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap) {
-    if (!weld_run_ready(c) || c->weld.doneSeq != c->runSeq) return PSGPU_RET_PARAM_ERROR;
+    if (!ctx_welded(c)) return PSGPU_RET_PARAM_ERROR;
     const int rc = set_device(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     return weld_download(c->weld, pos, nrm, col, tris, vertexMap);
 }
 
 int psgpu_weld_times(psgpu_ctx* c, float* ms, int maxPhases, const char** names) {
-    if (!c) return 0;
-    const int n = std::min(maxPhases, kWeldPhases);
-    for (int k = 0; k < n; ++k) {
-        if (ms) ms[k] = c->weld.lastMs[k];
-        if (names) names[k] = kWeldPhaseNames[k];
-    }
-    return n;
+    return c ? c->weld.times.report(ms, maxPhases, names, kWeldPhaseNames) : 0;
 }
 
 }  // extern "C"

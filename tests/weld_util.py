@@ -21,15 +21,35 @@ CASES = {
     # the same closed surface in a box that is no cube: a (6, 7, 5) lattice (tests/aniso_util.py)
     "rand3_0.071_box_6x7x5": ("boxed", 3, 0.071, None),
 }
+# Inputs for the branches of the shared mesh stages (psgpu_mesh_stages.h), kept out of CASES:
+# they have no entry in the golden count files, their counts stand here.
+# MPU prefix ranges of rand1_0.13 whose run vertices V, triangles T and welded vertices Vw
+# take every residue mod 4 between them (the 16-byte loads' scalar tails; [0, 26) is smaller
+# than one wave): name -> (V, T, Vw)
+TAIL_COUNTS = {
+    "rand1_0.13_mpus_0_26": (60, 91, 60),
+    "rand1_0.13_mpus_0_30": (73, 104, 73),
+    "rand1_0.13_mpus_0_32": (303, 461, 276),
+    "rand1_0.13_mpus_0_54": (1432, 2238, 1222),
+    "rand1_0.13_mpus_0_85": (2586, 3960, 2051),
+}
+# C2's model at half its cell size: more than 256 blocks of 256 in each of the weld's, the
+# shells' and the filter's scans (k_weld_scan's carry loop): (MPUs, V, T, Vw)
+SCAN_NAME = "C2_0.03125"
+SCAN_COUNTS = (50653, 126580, 194092, 97292)
+STAGE_CASES = {name: ("random", 1, 0.13, (0, int(name.rsplit("_", 1)[1]))) for name in TAIL_COUNTS}
+STAGE_CASES[SCAN_NAME] = ("config", "C2", 0.03125, None)
+
 BOXED_NAME = "rand3_0.071_box_6x7x5"
 BOX_LO, BOX_HI = (-1.35, -1.10, -1.03), (1.17, 1.95, 1.02)
 
 
 def make_case(name):
     """(model, cellsize, (mpu_begin, mpu_end or None))."""
-    kind, which, cs, rng = CASES[name]
+    kind, which, cs, rng = CASES[name] if name in CASES else STAGE_CASES[name]
     if kind == "config":
-        model, cs, _ = synth.make_config(which)
+        model, own, _ = synth.make_config(which)
+        cs = own if cs is None else cs
     else:
         model = synth.random_model(which, 6)
     if kind == "boxed":
