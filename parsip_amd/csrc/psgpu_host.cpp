@@ -17,7 +17,6 @@
 #include <functional>
 #include <limits>
 #include <memory>
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -381,7 +380,7 @@ LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
     brick_layout(c, &bi0, bd);
     in.sievable = c->cull != 0 && c->model.rootZeroValid != 0u && (uint64_t)bi0 + bd[0] <= (1u << 21) &&
                   bd[1] <= (1u << 21) && bd[2] <= (1u << 21);
-    if (const JitKernels* J = c->jit.get()) {
+    if (const JitKernels* J = c->jit.kernels.get()) {
         in.jit = true;
         in.hasPrecheckS = J->precheckS != nullptr;
         in.hasSurface = J->surface != nullptr;
@@ -429,7 +428,7 @@ Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
     p.scanStatusNext = c->scanStatus + (size_t)(c->parity ^ 1u) * kScanMaxBlocks;
     p.counts = c->counts;
     p.passed = c->passed;
-    p.bound = (c->bound && c->jit && c->model.boundable) ? 1u : 0u;
+    p.bound = (c->bound && c->jit.kernels && c->model.boundable) ? 1u : 0u;
     p.opInside = c->opInside ? 1u : 0u;
     p.mpuMasks = c->mpuMasks;
     p.offs = c->offs;
@@ -453,7 +452,7 @@ Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
     p.spans = (c->spans && c->spanNext < c->spanCap)
                   ? c->spans + (size_t)c->spanNext * 2 * kNumStampKernels * kSpanLanes : nullptr;
     p.mpuTicks = c->mpuTicksOpt ? c->mpuTicks : nullptr;
-    p.slotsPerLane = c->jit ? 0u : c->model.nSlots;
+    p.slotsPerLane = c->jit.kernels ? 0u : c->model.nSlots;
     p.debug = (uint32_t)c->debug;
     return p;
 }
@@ -468,7 +467,7 @@ hipError_t launch_jit(hipFunction_t f, uint32_t blocks, uint32_t threads, size_t
 // as k_surface.  No copies or fills.
 int launch_all(psgpu_ctx* c, const Params& pin, const LaunchPlan& plan, hipStream_t s, bool timed) {
     Params p = pin;
-    JitKernels* J = c->jit.get();
+    JitKernels* J = c->jit.kernels.get();
     // the split kernel's blocks hold 2 MPUs, the others 4 (mpu_lds_bytes(0): 4 MPUs' LDS)
     const size_t mpuLds = mpu_lds_bytes(0) / (plan.split ? 2 : 1);
     if (timed) PSGPU_CHECK(hipEventRecord(c->ev[0], s));
@@ -513,6 +512,38 @@ void drop_graphs(psgpu_ctx* c) {
     }
 }
 
+// Ahead of a change to what a run or a captured graph uses: wait for the pending run, drop the graphs.
+void quiesce(psgpu_ctx* c) {
+    if (c->pending) (void)hipStreamSynchronize(c->runStream);
+    drop_graphs(c);
+}
+
+// The counters of a run that found nothing: all zero, no overflow.
+DevCounters empty_counters() {
+    DevCounters d{};
+    d.firstOverflow = 0x7fffffff;
+    return d;
+}
+
+// The stamp buffer of `cap` waves a kernel (PSGPU_OPT_STAMPS): 24 bytes a wave per kernel, then 64 a wave.
+size_t stamp_bytes(size_t cap) { return (size_t)kNumStampKernels * cap * 24 + cap * 64; }
+
+// A finished run's counters over its shards: sums, and the largest shard's vertices and triangles.
+struct ShardSums {
+    uint32_t v = 0, t = 0, s = 0, p = 0, b = 0, maxV = 0, maxT = 0;
+    explicit ShardSums(const DevCounters& h) {
+        for (int k = 0; k < kShards; ++k) {
+            v += h.shard[k].v;
+            t += h.shard[k].t;
+            s += h.shard[k].s;
+            p += h.shard[k].p;
+            b += h.shard[k].b;
+            maxV = std::max(maxV, h.shard[k].v);
+            maxT = std::max(maxT, h.shard[k].t);
+        }
+    }
+};
+
 // Enqueue one polygonization: its shape is planned once, here, and kept as c->run.  k_precheck
 // needs nothing reset (k_finish of the previous run reset this run's counters) and k_finish
 // publishes the counters to mapped host memory.  Replayed from a hipGraph (one per counter
@@ -522,8 +553,7 @@ void reset_run_state(psgpu_ctx* c);
 int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
     if (c->mpuCount == 0) {  // nothing to launch: an empty result
         c->runTicks = c->mpuTicksOpt != 0;
-        memset(c->hostCtr, 0, sizeof(DevCounters));
-        c->hostCtr->firstOverflow = 0x7fffffff;
+        *c->hostCtr = empty_counters();
         // the totals the count exchange reads (k_finish writes them on a real run): zero
         // MPUs, no overflow -- never a previous run's
         PSGPU_CHECK(hipMemcpyAsync(c->totals, c->emptyTotals, 8 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
@@ -552,14 +582,14 @@ int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
     c->parity ^= 1u;  // k_finish of this run resets the other set for the next run
     const bool timed = c->timing != 0;
     if (c->stamps)  // waves that do not run leave no stale records
-        PSGPU_CHECK(hipMemsetAsync(c->stamps, 0, (size_t)kNumStampKernels * c->stampCap * 24 + (size_t)c->stampCap * 64, s));
+        PSGPU_CHECK(hipMemsetAsync(c->stamps, 0, stamp_bytes(c->stampCap), s));
     if (!c->useGraph || timed || s == nullptr) {
         const int rc = launch_all(c, p, plan, s, timed);
         if (rc != PSGPU_RET_SUCCESS) reset_run_state(c);
         return rc;
     }
     psgpu_ctx::GraphSlot& g = c->graphs[slot];
-    if (!(g.exec && g.jit == c->jit.get() && memcmp(&g.key, &p, sizeof(Params)) == 0 &&
+    if (!(g.exec && g.jit == c->jit.kernels.get() && memcmp(&g.key, &p, sizeof(Params)) == 0 &&
           memcmp(&g.plan, &plan, sizeof(LaunchPlan)) == 0)) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         g = psgpu_ctx::GraphSlot{};
@@ -577,7 +607,7 @@ int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
         (void)hipGraphDestroy(graph);
         PSGPU_CHECK(ei);
         g.key = p;
-        g.jit = c->jit.get();
+        g.jit = c->jit.kernels.get();
         g.plan = plan;
     }
     PSGPU_CHECK(hipGraphLaunch(g.exec, s));
@@ -623,91 +653,68 @@ void thread_results_add(uint64_t serial, uint32_t processed, uint32_t crossed) {
 // it).  Until then the interpreter runs; its output is bit-identical.  Call with the
 // context's device current.
 void jit_poll(psgpu_ctx* c, bool wait) {
-    if (!c->jitPending) return;
-    if (!wait && c->jitFut.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return;
-    std::shared_ptr<const JitCode> code = c->jitFut.get();
-    c->jitPending = false;
-    c->jitFut = JitFuture();
-    if (c->pending) (void)hipStreamSynchronize(c->runStream);
-    drop_graphs(c);
-    c->jit = jit_load(*code, c->device, &c->jitError);
-    if (!c->jit && code->code.size() && c->jitError.find("dropped") != std::string::npos) {
+    JitState& J = c->jit;
+    const auto code = J.compile.poll(wait);
+    if (!code) return;
+    quiesce(c);
+    J.kernels = jit_load(**code, c->device, &J.error);
+    if (!J.kernels && (*code)->code.size() && J.error.find("dropped") != std::string::npos) {
         // the cached object would not load: compile it afresh (bypassing the disk cache)
-        c->jitFut = jit_request(c->model, c->useJit == 2, false, c->opt.treeSplit != 0);
-        c->jitPending = true;
+        J.compile.start(jit_request(c->model, J.use == 2, false, c->opt.treeSplit != 0));
         if (wait) jit_poll(c, true);
         return;
     }
-    if (!c->jit) fprintf(stderr, "psgpu: JIT unavailable, using the interpreter: %s\n", c->jitError.c_str());
-    c->tier = c->jit ? (c->useJit == 2 ? 2 : 1) : 0;
+    if (!J.kernels) fprintf(stderr, "psgpu: JIT unavailable, using the interpreter: %s\n", J.error.c_str());
+    J.tier = J.kernels ? (J.use == 2 ? 2 : 1) : 0;
 }
 
 // PSGPU_OPT_JIT 3: adopt the baked kernels once their compile has finished (wait: block).
 void tier_poll(psgpu_ctx* c, bool wait) {
-    if (!c->tier2Pending) return;
-    if (!wait && c->tier2Fut.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return;
-    std::shared_ptr<const JitCode> code = c->tier2Fut.get();
-    c->tier2Pending = false;
-    c->tier2Fut = JitFuture();
+    JitState& J = c->jit;
+    const auto code = J.baked.poll(wait);
+    if (!code) return;
     std::string err;
-    std::shared_ptr<JitKernels> k = jit_load(*code, c->device, &err);
+    std::shared_ptr<JitKernels> k = jit_load(**code, c->device, &err);
     if (!k) {  // the structure kernels keep serving this model
-        c->tier2Failed = true;
+        J.tier2Failed = true;
         fprintf(stderr, "psgpu: baked kernels unavailable, the structure kernels stay: %s\n", err.c_str());
         return;
     }
     if (c->pending && c->useGraph) (void)hipStreamSynchronize(c->runStream);  // no graph dies in flight
     drop_graphs(c);  // modules live as long as the process: in-flight runs keep theirs
-    c->jit1 = c->jit;
-    c->jit = k;
-    c->tier = 2;
+    J.kernels1 = J.kernels;
+    J.kernels = k;
+    J.tier = 2;
 }
 
 // PSGPU_OPT_JIT 3: count a run of the unchanged model on the structure kernels and start the
 // baked compile at the threshold.
 void tier_count(psgpu_ctx* c) {
-    if (c->useJit != 3 || c->tier != 1 || c->tier2Pending || c->tier2Failed) return;
-    if (++c->staticRuns < c->tierRuns) return;
-    c->tier2Fut = jit_request(c->model, true, true, c->opt.treeSplit != 0);
-    c->tier2Pending = true;
+    JitState& J = c->jit;
+    if (J.use != 3 || J.tier != 1 || J.baked.pending() || J.tier2Failed) return;
+    if (++J.staticRuns < J.tierRuns) return;
+    J.baked.start(jit_request(c->model, true, true, c->opt.treeSplit != 0));
 }
 
-// Start (or restart) the compile of the current model's kernels.
+// Start (or restart) the compile of the current model's kernels.  A compile still running for
+// the previous model or options is retired: it ends in the background, before the context goes.
 void jit_start(psgpu_ctx* c) {
-    c->jit.reset();
-    c->jit1.reset();
-    // a compile still running for the previous model or options finishes in the background, and
-    // psgpu_destroy waits for it: a hiprtc thread left running into process exit can outlive
-    // the compiler's own lazily built statics (a core dump after a run that changed options
-    // under a compile, tools/fuzz_parity.py in round 6)
-    if (c->jitPending && c->jitFut.valid()) c->retired.push_back(c->jitFut);
-    c->jitPending = false;
-    c->jitFut = JitFuture();
-    c->tier = 0;
-    c->staticRuns = 0;
-    c->tier2Failed = false;
-    if (c->tier2Pending) c->retired.push_back(c->tier2Fut);  // finishes in the background
-    c->tier2Pending = false;
-    c->tier2Fut = JitFuture();
-    for (size_t i = 0; i < c->retired.size();) {  // forget the finished ones
-        if (c->retired[i].wait_for(std::chrono::seconds(0)) == std::future_status::ready) {
-            c->retired.erase(c->retired.begin() + (long)i);
-        } else {
-            ++i;
-        }
-    }
-    if (!c->useJit || !c->haveModel) return;
-    c->jitFut = jit_request(c->model, c->useJit == 2, true, c->opt.treeSplit != 0);
-    c->jitPending = true;
-    jit_poll(c, !c->jitAsync);
+    JitState& J = c->jit;
+    J.kernels.reset();
+    J.kernels1.reset();
+    J.tier = J.staticRuns = 0;
+    J.tier2Failed = false;
+    J.compile.drop();
+    J.baked.drop();
+    if (!J.use || !c->haveModel) return;
+    J.compile.start(jit_request(c->model, J.use == 2, true, c->opt.treeSplit != 0));
+    jit_poll(c, !J.async);
 }
 
 // Put a context whose launch sequence failed part-way back into a usable state: the
 // next run's counters and look-back words were to be reset by this run's k_finish.
 void reset_run_state(psgpu_ctx* c) {
-    DevCounters init[2];
-    memset(init, 0, sizeof(init));
-    init[0].firstOverflow = init[1].firstOverflow = 0x7fffffff;
+    const DevCounters init[2] = {empty_counters(), empty_counters()};
     (void)hipStreamSynchronize(c->stream);
     (void)hipMemcpy(c->ctr, init, sizeof(init), hipMemcpyHostToDevice);
     (void)hipMemset(c->scanStatus, 0, 2 * kScanMaxBlocks * sizeof(uint64_t));
@@ -911,33 +918,23 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
         psgpu_destroy(c);
         return PSGPU_RET_DEVICE_ERROR;
     }
-    memset(c->hostCtr, 0, sizeof(DevCounters));
-    c->hostCtr->firstOverflow = 0x7fffffff;
+    *c->hostCtr = empty_counters();
     c->emptyTotals = c->totals + 8;  // {0, 0, 0, 0, 0, 0, no overflow, no error}
-    {
-        const uint32_t empty[16] = {0, 0, 0, 0, 0, 0, 0x7fffffffu, 0, 0, 0, 0, 0, 0, 0, 0x7fffffffu, 0};
-        if (hipMemcpy(c->totals, empty, sizeof(empty), hipMemcpyHostToDevice) != hipSuccess) {
-            psgpu_destroy(c);
-            return PSGPU_RET_DEVICE_ERROR;
-        }
-    }
-    {
-        DevCounters init[2];
-        memset(init, 0, sizeof(init));
-        init[0].firstOverflow = init[1].firstOverflow = 0x7fffffff;
-        if (hipMemcpy(c->ctr, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) {
-            psgpu_destroy(c);
-            return PSGPU_RET_DEVICE_ERROR;
-        }
+    const uint32_t empty[16] = {0, 0, 0, 0, 0, 0, 0x7fffffffu, 0, 0, 0, 0, 0, 0, 0, 0x7fffffffu, 0};
+    const DevCounters init[2] = {empty_counters(), empty_counters()};
+    if (hipMemcpy(c->totals, empty, sizeof(empty), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->ctr, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) {
+        psgpu_destroy(c);
+        return PSGPU_RET_DEVICE_ERROR;
     }
     for (int i = 0; i <= kNumKernels; ++i) (void)hipEventCreate(&c->ev[i]);
     const char* cullEnv = getenv("PSGPU_CULL");
     if (cullEnv) c->cull = atoi(cullEnv) != 0;
     if (const char* e = getenv("PSGPU_OP_INSIDE")) c->opInside = atoi(e) != 0;
     const char* jitEnv = getenv("PSGPU_JIT");
-    if (jitEnv) c->useJit = std::min(3, std::max(0, atoi(jitEnv)));
+    if (jitEnv) c->jit.use = std::min(3, std::max(0, atoi(jitEnv)));
     const char* asyncEnv = getenv("PSGPU_JIT_ASYNC");
-    if (asyncEnv) c->jitAsync = atoi(asyncEnv) != 0;
+    if (asyncEnv) c->jit.async = atoi(asyncEnv) != 0;
     if (const char* e = getenv("PSGPU_GRID_FIT")) c->opt.gridFit = atoi(e) != 0;          // 0: persistent grids
     if (const char* e = getenv("PSGPU_FINISH_QUAD")) c->opt.finishQuad = std::min(3, std::max(0, atoi(e)));
     if (const char* e = getenv("PSGPU_VERTEX_WIDE")) c->opt.vertexWide = std::min(2, std::max(0, atoi(e)));
@@ -955,16 +952,9 @@ void psgpu_destroy(psgpu_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     set_pending(c, false);
     drop_graphs(c);
-    // an in-flight hiprtc compile must not outlive its owner: a process that exits while
-    // LLVM compiles on the job thread tears LLVM's statics down under it
-    if (c->jitPending && c->jitFut.valid()) c->jitFut.wait();
-    if (c->tier2Pending && c->tier2Fut.valid()) c->tier2Fut.wait();
-    for (JitFuture& f : c->retired)
-        if (f.valid()) f.wait();
-    c->jitFut = JitFuture();
-    c->tier2Fut = JitFuture();
-    c->jit.reset();
-    c->jit1.reset();
+    // no compile outlives its context (psgpu_compile.h), and they end ahead of the stream
+    c->jit.compile.drain();
+    c->jit.baked.drain();
     weld_state_free(c->weld);
     for (int i = 0; i <= kNumKernels; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1010,11 +1000,10 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
     else if (option == PSGPU_OPT_VERTEX_WIDE && value >= 0 && value <= 2) c->opt.vertexWide = (int)value;
     else if (option == PSGPU_OPT_TREE_SPLIT && value >= 0 && value <= 2) {
         const bool recompile = value != 0 && c->opt.treeSplit == 0 && c->haveModel && c->splittable &&
-                               !(c->jit && c->jit->precheckS);
+                               !(c->jit.kernels && c->jit.kernels->precheckS);
         c->opt.treeSplit = (int)value;
         if (recompile) {  // the loaded kernels lack the split variants: generate them
-            if (c->pending) (void)hipStreamSynchronize(c->runStream);
-            drop_graphs(c);
+            quiesce(c);
             jit_start(c);
         }
     }
@@ -1022,22 +1011,20 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
     else if (option == PSGPU_OPT_FUSED_SURFACE && value >= 0 && value <= 3) c->opt.fusedSurface = (int)value;
     else if (option == PSGPU_OPT_FRONT && value >= 0 && value <= 2) c->opt.front = (int)value;
     else if (option == PSGPU_OPT_SIEVE && value >= 0 && value <= 2) c->opt.sieve = (int)value;
-    else if (option == PSGPU_OPT_TIER_RUNS && value >= 1 && value <= (1 << 30)) c->tierRuns = (int)value;
+    else if (option == PSGPU_OPT_TIER_RUNS && value >= 1 && value <= (1 << 30)) c->jit.tierRuns = (int)value;
     else if (option == PSGPU_OPT_JIT) {
         if (value < 0 || value > 3) return PSGPU_RET_PARAM_ERROR;
-        c->useJit = (int)value;
-        if (c->pending) (void)hipStreamSynchronize(c->runStream);
-        drop_graphs(c);
+        c->jit.use = (int)value;
+        quiesce(c);
         jit_start(c);
     }
-    else if (option == PSGPU_OPT_JIT_ASYNC) c->jitAsync = value != 0;
+    else if (option == PSGPU_OPT_JIT_ASYNC) c->jit.async = value != 0;
     else if (option == PSGPU_OPT_MPU_TICKS) c->mpuTicksOpt = value != 0;  // buffers: next polygonize
     else if (option == PSGPU_OPT_SPANS && value >= 0 && value <= (1 << 20)) {
         // the next `value` runs record their kernel spans, one slot each (then none)
-        if (c->pending) (void)hipStreamSynchronize(c->runStream);
+        quiesce(c);
         c->spans.release();
         c->spanCap = c->spanNext = 0;
-        drop_graphs(c);
         if (value > 0) {
             std::vector<uint64_t> init((size_t)value * 2 * kNumStampKernels * kSpanLanes);
             for (size_t i = 0; i < init.size(); i += 2) {
@@ -1050,12 +1037,11 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
         }
     }
     else if (option == PSGPU_OPT_STAMPS && value >= 0 && value <= (1 << 24)) {
-        if (c->pending) (void)hipStreamSynchronize(c->runStream);
+        quiesce(c);
         c->stamps.release();
         c->stampCap = 0;
-        drop_graphs(c);
         if (value > 0) {
-            const size_t bytes = (size_t)kNumStampKernels * value * 24 + (size_t)value * 64;
+            const size_t bytes = stamp_bytes((size_t)value);
             PSGPU_CHECK(c->stamps.reserve(bytes / 8, Growth::Exact));  // whole 8-byte words
             PSGPU_CHECK(hipMemset(c->stamps, 0, bytes));  // a kernel a run does not launch leaves no rows
             c->stampCap = (uint32_t)value;
@@ -1089,7 +1075,7 @@ int psgpu_set_model(psgpu_ctx* c, const PsSoaBlobPrims* prims, const PsSoaPrimMa
     }
     c->haveModel = true;
     ++c->runSeq;  // a weld belongs to a finished run of the current model
-    if (!same || (!c->jit && !c->jitPending)) jit_start(c);
+    if (!same || (!c->jit.kernels && !c->jit.compile.pending())) jit_start(c);
     return PSGPU_RET_SUCCESS;
 }
 
@@ -1164,14 +1150,8 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
         bool reran = false;
         for (int attempt = 0; attempt < 4; ++attempt) {
             const DevCounters& h = *c->hostCtr;
-            uint32_t V = 0, T = 0, mv = 0, mt = 0, Q = 0;
-            for (int k = 0; k < kShards; ++k) {
-                V += h.shard[k].v;
-                T += h.shard[k].t;
-                Q += h.shard[k].p;
-                mv = std::max(mv, h.shard[k].v);
-                mt = std::max(mt, h.shard[k].t);
-            }
+            const ShardSums sum(h);
+            const uint32_t V = sum.v, T = sum.t, mv = sum.maxV, mt = sum.maxT, Q = sum.p;
             bool gridShort = c->mpuCount > 0 && Q > c->run.mpb * c->run.mpuBlocks;
             if (c->run.front) {  // k_front: each sub-queue against its own rows of S2 blocks
                 uint32_t sub = 0;
@@ -1228,23 +1208,16 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
             c->debug &= ~(1 << 21);
             return PSGPU_RET_DEVICE_ERROR;
         }
-        uint32_t V = 0, T = 0, S = 0, P = 0, Q = 0;
-        for (int k = 0; k < kShards; ++k) {
-            V += h.shard[k].v;
-            T += h.shard[k].t;
-            S += h.shard[k].s;
-            P += h.shard[k].p + h.shard[k].b;
-            Q += h.shard[k].p;
-        }
+        const ShardSums sum(h);
         PsMeshInfo& I = c->info;
         memset(&I, 0, sizeof(I));
         I.ctMPUs = c->mpuCount;
-        I.ctPassedPrecheck = c->mpuCount ? P : 0;
-        I.ctSurfaceMPUs = c->mpuCount ? S : 0;
-        I.ctVertices = c->mpuCount ? V : 0;
-        I.ctTriangles = c->mpuCount ? T : 0;
+        I.ctPassedPrecheck = c->mpuCount ? sum.p + sum.b : 0;
+        I.ctSurfaceMPUs = c->mpuCount ? sum.s : 0;
+        I.ctVertices = c->mpuCount ? sum.v : 0;
+        I.ctTriangles = c->mpuCount ? sum.t : 0;
         I.firstOverflowMPU = (c->mpuCount && h.firstOverflow != 0x7fffffff) ? h.firstOverflow : -1;
-        I.ctFieldMPUs = c->mpuCount ? Q : 0;
+        I.ctFieldMPUs = c->mpuCount ? sum.p : 0;
         I.ctLaneEvals = 8ull * c->mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
         I.launchFlags = c->mpuCount == 0 ? 0u
                         : (c->run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
@@ -1264,8 +1237,7 @@ int psgpu_download_stamps(psgpu_ctx* c, uint64_t* out, uint32_t* capOut) {
     if (rc != PSGPU_RET_SUCCESS) return rc;
     if (capOut) *capOut = c->stamps ? c->stampCap : 0u;
     if (!c->stamps || !out) return c->stamps ? PSGPU_RET_SUCCESS : PSGPU_RET_PARAM_ERROR;
-    PSGPU_CHECK(hipMemcpy(out, c->stamps, (size_t)kNumStampKernels * c->stampCap * 24 + (size_t)c->stampCap * 64,
-                          hipMemcpyDeviceToHost));
+    PSGPU_CHECK(hipMemcpy(out, c->stamps, stamp_bytes(c->stampCap), hipMemcpyDeviceToHost));
     return PSGPU_RET_SUCCESS;
 }
 
@@ -1273,14 +1245,11 @@ int psgpu_vertex_queue(psgpu_ctx* c, uint32_t* counts, uint32_t* recs, uint32_t 
     if (!c || !counts) return PSGPU_RET_PARAM_ERROR;
     int rc = psgpu_finish(c, nullptr);
     if (rc != PSGPU_RET_SUCCESS) return rc;
-    uint64_t total = 0;
-    for (int k = 0; k < kShards; ++k) {
-        counts[k] = c->mpuCount ? c->hostCtr->shard[k].v : 0u;
-        if (counts[k] > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;  // finish re-runs until they fit
-        total += counts[k];
-    }
+    for (int k = 0; k < kShards; ++k) counts[k] = c->mpuCount ? c->hostCtr->shard[k].v : 0u;
+    const ShardSums sum(*c->hostCtr);
+    if (c->mpuCount && sum.maxV > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;  // finish re-runs until they fit
     if (!recs) return PSGPU_RET_SUCCESS;
-    if (total > capacity) return PSGPU_RET_PARAM_ERROR;
+    if (c->mpuCount && sum.v > capacity) return PSGPU_RET_PARAM_ERROR;
     rc = set_device(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     std::vector<VertexKey> shard;
@@ -1918,9 +1887,9 @@ int psgpu_field_values(psgpu_ctx* c, const float* xyz, uint32_t n, int mode, flo
     PSGPU_CHECK(hipMemcpy(dx, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
     Params p = make_params(c, plan_run(c, false));
     hipError_t e;
-    if (c->jit) {
+    if (c->jit.kernels) {
         void* args[] = {&p, &dx, &dout, &dcol, &n, &mode};
-        e = hipModuleLaunchKernel(c->jit->probe, (n + 255) / 256, 1, 1, 256, 1, 1, 0, c->stream, args, nullptr);
+        e = hipModuleLaunchKernel(c->jit.kernels->probe, (n + 255) / 256, 1, 1, 256, 1, 1, 0, c->stream, args, nullptr);
     } else {
         e = launch_probe(p, c->stream, dx, dout, dcol, n, mode);
     }
@@ -1959,41 +1928,24 @@ long psgpu_model_image(const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* mat
     return (long)sizeof(DevModel);
 }
 
+// The context's JIT state once whatever has finished compiling is adopted (wait: block for it).
+static JitState& jit_now(psgpu_ctx* c, bool wait) {
+    if ((c->jit.compile.pending() || c->jit.baked.pending()) && set_device(c) == PSGPU_RET_SUCCESS) {
+        jit_poll(c, wait);
+        tier_poll(c, wait);
+    }
+    return c->jit;
+}
 // Whether the current model runs on run-time specialised kernels (1) or the interpreter (0).
-int psgpu_jit_active(psgpu_ctx* c) {
-    if (!c) return 0;
-    if (c->jitPending && set_device(c) == PSGPU_RET_SUCCESS) jit_poll(c, false);
-    return c->jit ? 1 : 0;
-}
-
-int psgpu_jit_pending(psgpu_ctx* c) {
-    if (!c) return 0;
-    if (c->jitPending && set_device(c) == PSGPU_RET_SUCCESS) jit_poll(c, false);
-    return c->jitPending ? 1 : 0;
-}
-
-int psgpu_jit_wait(psgpu_ctx* c) {
-    if (!c) return 0;
-    if ((c->jitPending || c->tier2Pending) && set_device(c) == PSGPU_RET_SUCCESS) {
-        jit_poll(c, true);
-        tier_poll(c, true);
-    }
-    return c->jit ? 1 : 0;
-}
-
-int psgpu_jit_tier(psgpu_ctx* c) {
-    if (!c) return 0;
-    if ((c->jitPending || c->tier2Pending) && set_device(c) == PSGPU_RET_SUCCESS) {
-        jit_poll(c, false);
-        tier_poll(c, false);
-    }
-    return c->tier;
-}
+int psgpu_jit_active(psgpu_ctx* c) { return c && jit_now(c, false).kernels ? 1 : 0; }
+int psgpu_jit_pending(psgpu_ctx* c) { return c && jit_now(c, false).compile.pending() ? 1 : 0; }
+int psgpu_jit_wait(psgpu_ctx* c) { return c && jit_now(c, true).kernels ? 1 : 0; }
+int psgpu_jit_tier(psgpu_ctx* c) { return c ? jit_now(c, false).tier : 0; }
 
 // Generated specialised source for the current model (NUL-terminated, truncated to cap).
 int psgpu_jit_source(psgpu_ctx* c, char* buf, size_t cap) {
     if (!c || !c->haveModel) return PSGPU_RET_PARAM_ERROR;
-    const std::string s = jit_source(c->model, c->tier == 2 || c->useJit == 2, c->opt.treeSplit != 0);
+    const std::string s = jit_source(c->model, c->jit.tier == 2 || c->jit.use == 2, c->opt.treeSplit != 0);
     if (buf && cap) {
         const size_t n = std::min(cap - 1, s.size());
         memcpy(buf, s.data(), n);

@@ -90,7 +90,6 @@ struct WeldState {
 
 struct psgpu_ctx {
     using JitKernels = psgpu::JitKernels;
-    using JitFuture = psgpu::JitFuture;
     using DevModel = psgpu::DevModel;
     using Params = psgpu::Params;
     using DevCounters = psgpu::DevCounters;
@@ -108,27 +107,12 @@ struct psgpu_ctx {
     DevModel model{};
     psgpu::DevBuf<DevModel> dModel;
     psgpu::DevBuf<CubeTablesDev> dTables;
-    int useJit = 1;
-    int jitAsync = 1;                  // set_model returns while hiprtc compiles (interpreter meanwhile)
-    std::shared_ptr<JitKernels> jit;   // specialised kernels of the current model
-    JitFuture jitFut;                  // the current model's compile, while jitPending
-    bool jitPending = false;
-    std::string jitError;
+    psgpu::JitState jit;  // the model's run-time kernels, their tier and their compiles (psgpu_jit.h)
     // this run enqueued while no other run of the process was pending on the device (a
     // blocking caller): the layout defaults pick the shorter-span (latency) layouts
     bool alone = false;
     // ... or while 4 or more other contexts have runs pending on it: no in-kernel waits then
     bool crowded = false;
-    // PSGPU_OPT_JIT 3 (tiered): once the model has stayed unchanged for tierRuns runs, its
-    // baked kernels compile on a host thread and replace the structure kernels (kept in jit1)
-    int tier = 0;                      // what `jit` holds: 0 none, 1 structure, 2 baked kernels
-    int tierRuns = 16;
-    int staticRuns = 0;                // runs of the current model on the structure kernels
-    JitFuture tier2Fut;                // the baked compile, while tier2Pending
-    bool tier2Pending = false;
-    bool tier2Failed = false;          // the baked compile failed: stay on tier 1 for this model
-    std::shared_ptr<JitKernels> jit1;  // the structure kernels while tier 2 serves
-    std::vector<JitFuture> retired;    // baked compiles of models since replaced (destroy waits)
     bool haveModel = false;
     int cull = 1;
     int debug = 0;

@@ -2,11 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <future>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "psgpu_compile.h"
 #include "psgpu_model.h"
 
 namespace psgpu {
@@ -29,7 +29,26 @@ struct JitCode {
     std::vector<char> code;  // empty on failure
     std::string error;
 };
-using JitFuture = std::shared_future<std::shared_ptr<const JitCode>>;
+using JitSlot = CompileSlot<std::shared_ptr<const JitCode>>;
+using JitFuture = JitSlot::Future;
+
+// A polygonizer context's run-time kernels and their compiles (psgpu_host.cpp: jit_start,
+// jit_poll, tier_poll, tier_count).  PSGPU_OPT_JIT 3 (tiered): once the model has stayed
+// unchanged for tierRuns runs, its baked kernels compile on a host thread and replace the
+// structure kernels (kept in kernels1).
+struct JitState {
+    int use = 1;                          // PSGPU_OPT_JIT
+    int async = 1;                        // set_model returns while hiprtc compiles (interpreter meanwhile)
+    std::shared_ptr<JitKernels> kernels;  // specialised kernels of the current model
+    std::string error;
+    int tier = 0;                         // what `kernels` holds: 0 none, 1 structure, 2 baked kernels
+    int tierRuns = 16;
+    int staticRuns = 0;                   // runs of the current model on the structure kernels
+    bool tier2Failed = false;             // the baked compile failed: stay on tier 1 for this model
+    std::shared_ptr<JitKernels> kernels1;  // the structure kernels while tier 2 serves
+    JitSlot compile;                      // the current model's kernels, while they compile
+    JitSlot baked;                        // its baked tier
+};
 
 // Request the model's specialised kernels: hiprtc compiles on a host thread (one job per
 // distinct source; an on-disk cache serves repeats unless useDisk is false).  No GPU needed.
@@ -45,7 +64,10 @@ std::string jit_source(const DevModel& m, bool baked, bool split = false);
 // the generated walk splits at the root (TreeEval::kSplit): a binary known op over two ops
 bool jit_splittable(const DevModel& m);
 // Compat mode: compile a generated compact-tree source (psgpu_gui_jit.cpp) against the
-// embedded compat headers, with the same on-disk cache.  Blocking; no GPU needed.
+// embedded compat headers, with the same on-disk cache, on a host thread (jobs are neither
+// deduplicated nor retained: an editor session makes a new source per edit); the second form
+// waits for it.  No GPU needed.
+JitFuture jit_request_gui(const std::string& src);
 bool jit_compile_gui(const std::string& src, std::vector<char>& code, std::string* err);
 
 }  // namespace psgpu

@@ -256,3 +256,33 @@ def test_export_thread_pool(tmp_path):
                     os.path.join(ROOT, "tests", "cpp", "pool_check.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
+def test_compile_slot(tmp_path):
+    """The owner of a pending compile (psgpu_compile.h), from that header alone: start and drop
+    never wait, poll hands a result out once, drain and the destructor wait for the pending job
+    and every retired one -- plain, under ASan + UBSan, and under TSan.  TSan's runtime cannot
+    map its shadow memory under some kernels' address-space randomisation and then ends before
+    main ("unexpected memory mapping"): that build runs again without randomisation, and only a
+    host on which it still cannot start goes without the TSan run."""
+    import platform
+    import shutil
+    import subprocess
+
+    gpp = shutil.which("g++")
+    if gpp is None:
+        pytest.skip("no g++")
+    no_tsan = "ThreadSanitizer: unexpected memory mapping"
+    for k, flags in enumerate(([], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                               ["-fsanitize=thread"])):
+        exe = tmp_path / f"compile_check{k}"
+        subprocess.run([gpp, "-std=c++17", "-O2", "-g", "-Wall", "-pthread", *flags,
+                        "-I", os.path.join(ROOT, "parsip_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "cpp", "compile_check.cpp"), "-o", str(exe)], check=True)
+        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+        if no_tsan in r.stderr and shutil.which("setarch"):
+            r = subprocess.run(["setarch", platform.machine(), "-R", str(exe)], capture_output=True, text=True,
+                               timeout=120)
+        if no_tsan in r.stderr:
+            continue
+        assert r.returncode == 0 and r.stdout.strip() == "ok", f"{flags}: " + r.stdout + r.stderr
