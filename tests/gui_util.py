@@ -137,3 +137,12 @@ def assert_gui_mesh_equal(gm, om, what=""):
         g, o = bits(getattr(gm, name)), bits(getattr(om, name))
         bad = np.nonzero(g != o)[0]
         assert len(bad) == 0, (what, name, len(bad), getattr(gm, name).ravel()[bad[:4]], getattr(om, name).ravel()[bad[:4]])
+
+
+def assert_info_equal(a, b):
+    """Two PsGuiInfo, field by field."""
+    for f, _ in gui.PsGuiInfo._fields_:
+        va, vb = getattr(a, f), getattr(b, f)
+        if f == "dims":
+            va, vb = list(va), list(vb)
+        assert va == vb, (f, va, vb)

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import psgui
-from gui_util import assert_gui_mesh_equal, bits, random_ext_tree, random_tree
+from gui_util import assert_gui_mesh_equal, assert_info_equal as _info_equal, bits, random_ext_tree, random_tree
 from parsip_amd import blobtree as bt
 from parsip_amd import gui, scene
 
@@ -376,14 +376,6 @@ def _both(ctx, tree, cs, iso=0.5, octree=None):
     gm = ctx.exportMesh()
     om = psgui.polygonize(tree, lo, hi, cs, iso, threads=8)
     return gm, om
-
-
-def _info_equal(a, b):
-    for f, _ in gui.PsGuiInfo._fields_:
-        va, vb = getattr(a, f), getattr(b, f)
-        if f == "dims":
-            va, vb = list(va), list(vb)
-        assert va == vb, (f, va, vb)
 
 
 @pytest.mark.gpu
