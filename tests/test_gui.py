@@ -543,6 +543,59 @@ def test_gpu_random_ext_trees_bit_exact(seed):
 
 
 @pytest.mark.gpu
+def test_gpu_kernel_sets_in_one_context():
+    """One context through every kernel set in turn (the other tests make a context per
+    configuration): interpreter, generated, the extended walk of a PCM tree, generated again
+    (a module loaded after one was unloaded), and back to the interpreter by option alone.
+    After each step the mesh, statistics and offsets, and a 257-point field / colour probe,
+    are bit-exact with the oracle."""
+    cs = 0.12
+    xyz_rng = np.random.default_rng(12)
+    p = _ext_ctx(0)
+
+    def set_jit(mode):
+        assert p._L.psgpu_gui_set_option(p._g, gui.OPT_JIT, mode) == 1  # PSGPU_RET_SUCCESS
+
+    def probe(tree, what, state=None):
+        xyz = xyz_rng.uniform(*tree.root_octree, size=(257, 3)).astype(np.float32)
+        gf, gc = p.field_values(xyz)
+        of, oc = psgui.field_values(tree, xyz, pcm_state=state)
+        assert np.array_equal(bits(gf), bits(of)) and np.array_equal(bits(gc), bits(oc)), what
+        assert np.count_nonzero(gf) > 0, what
+
+    def step(tree, status, what):
+        lo, hi = tree.root_octree
+        p.setup(tree, (lo, hi), 0, cs, 0.5)
+        assert p.jit_status() == status, what
+        p.run()
+        om = psgui.polygonize(tree, lo, hi, cs, 0.5, threads=8)
+        assert om.info.ctLatticeMPUs >= 100 and om.info.ctTriangles > 0, what
+        _info_equal(p.finish(), om.info)
+        assert_gui_mesh_equal(p.exportMesh(), om, what)
+        assert p.jit_status() == status, what
+        probe(tree, what)
+
+    try:
+        _, tree_a = gui.compact_blobtree(random_tree(3, n_prims=12))
+        # seed 5, not 4: seed 4's root octree is flat in y, its lattice at this cell size empty
+        _, tree_b = gui.compact_blobtree(random_tree(5, n_prims=12))
+        _, tree_pcm = gui.compact_blobtree(_pcm_pair())
+        p.set_tree(tree_a)
+        step(tree_a, gui.JIT_NONE, "1: interpreter")
+        set_jit(2)
+        p.set_tree(tree_a)  # the same tree again: its kernels compile, set_tree waits for them
+        step(tree_a, gui.JIT_ACTIVE, "2: generated")
+        state = _ext_runs(p, tree_pcm, 0.03, runs=2)  # 240 MPUs; asserts JIT_NONE: the extended walk
+        assert state[0] > 0.5 and state[1] > 0.5
+        probe(tree_pcm, "3: extended", state=state)
+        step(tree_b, gui.JIT_ACTIVE, "4: generated again")
+        set_jit(0)
+        step(tree_b, gui.JIT_NONE, "5: interpreter by option")
+    finally:
+        p.close()
+
+
+@pytest.mark.gpu
 def test_gpu_ext_probe_reads_state():
     p = _ext_ctx(0)
     try:

@@ -258,6 +258,33 @@ def test_export_thread_pool(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
 
 
+def test_gui_tree_check(tmp_path):
+    """The compat mode's host-only half (psgpu_gui_tree.h: which caller-supplied trees are
+    accepted, and the candidate tables) from that header and psgpu_gui_cull.cpp alone, with
+    g++ and no ROCm include path: every array in an allocation of exactly its stated size,
+    plain and under ASan + UBSan.  The same table of cases then runs through the library's
+    psgpu_gui_cull_boxes, which must return the same codes."""
+    import shutil
+    import subprocess
+
+    gpp = shutil.which("g++")
+    if gpp is None:
+        pytest.skip("no g++")
+    csrc = os.path.join(ROOT, "parsip_amd", "csrc")
+    tri = tmp_path / "tritable.txt"
+    tri.write_text(" ".join(str(int(v)) for v in np.asarray(gpu.tritable()).ravel()))
+    base = [gpp, "-std=c++17", "-O2", "-g", "-Wall", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "gui_tree_check.cpp")]
+    lib_dir = os.path.join(ROOT, "parsip_amd")
+    builds = ([os.path.join(csrc, "psgpu_gui_cull.cpp")],
+              ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(csrc, "psgpu_gui_cull.cpp")],
+              ["-DGUI_TREE_VIA_LIBRARY", "-L", lib_dir, "-l:libparsip_gpu.so", f"-Wl,-rpath,{lib_dir}"])
+    for k, extra in enumerate(builds):
+        exe = tmp_path / f"gui_tree_check{k}"
+        subprocess.run([*base, *extra, "-o", str(exe)], check=True)
+        r = subprocess.run([str(exe), str(tri)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.strip() == "ok", f"{extra[0]}: " + r.stdout + r.stderr
+
+
 def test_compile_slot(tmp_path):
     """The owner of a pending compile (psgpu_compile.h), from that header alone: start and drop
     never wait, poll hands a result out once, drain and the destructor wait for the pending job
