@@ -151,6 +151,56 @@ int  psgpu_gui_finish(psgpu_gui* g, PsGuiInfo* info);
 int  psgpu_gui_download(psgpu_gui* g, float* pos, float* nrm, float* col4, uint32_t* tris,
                         uint64_t* mpuOffsets, PsGuiMpuStats* stats);
 
+/* The weld of the finished run's mesh, its shells and its filter, on the device: the hot
+ * path's psgpu_weld / psgpu_weld_shells / psgpu_weld_filter families (parsip_gpu.h: their
+ * structs, rules and reproducibility hold here) over this context's mesh.
+ *
+ * The Newton root (ComputeRootNewtonRaphsonVEC4) starts at the edge's corner nearer the iso
+ * value and steps along the full gradient: a vertex does not stay on its lattice edge, two
+ * edges that share their start corner can get the same position bits, and the copies that
+ * neighbouring MPUs make of one edge's vertex differ in the last bits.  So no comparison of
+ * positions welds this mesh; the identity is the edge itself.  Every vertex belongs to one
+ * global lattice edge (gx, gy, gz, axis): MPU m = (i * dims[1] + j) * dims[2] + k created it
+ * on its local edge from corner (ci, cj, ck) along `axis` (0 x, 1 y, 2 z), and
+ * (gx, gy, gz) = (7 i + ci, 7 j + cj, 7 k + ck).
+ *
+ * The weld's definition: vertices with equal lattice edges are one welded vertex; welded
+ * vertices are ordered by their smallest input index and take that vertex's position, normal
+ * and rgba bit for bit; vertexMap[v] is the welded id of input vertex v; the triangles are
+ * vertexMap[tris], in order, and none is dropped; seams towards MPUs that were not processed
+ * stay open.  Two welds of one run give the same bytes.
+ *
+ * A weld needs a finished run (psgpu_gui_finish or psgpu_gui_download after the last
+ * psgpu_gui_polygonize) that no psgpu_gui_set_tree or psgpu_gui_polygonize has superseded,
+ * on a lattice with 7 * dims[a] < 2^20: PSGPU_RET_PARAM_ERROR otherwise.  The shells need the
+ * current run's weld, the filter its shells (PSGPU_RET_PARAM_ERROR).  An empty mesh welds to
+ * an empty mesh.  Colours stay rgba: `col` of PsWeldDevice and PsFilterDevice is 4 floats a
+ * vertex for this context, as col4 of the downloads.  The device pointers are valid until
+ * the next call of the same or an earlier stage, or psgpu_gui_destroy.
+ *
+ * psgpu_gui_download_edges: (gx, gy, gz, axis) of every vertex of the finished run, 4 words a
+ * vertex, those inside an MPU included (the only place a caller learns them).
+ * psgpu_gui_weld_times: psgpu_weld_times' phases ("weld total" spans those five launches),
+ * then "k_gui_weld_edges", the kernel that names the edges ahead of them. */
+int  psgpu_gui_download_edges(psgpu_gui* g, uint32_t* edges4);
+int  psgpu_gui_weld(psgpu_gui* g, PsWeldInfo* info);
+int  psgpu_gui_weld_device(psgpu_gui* g, PsWeldDevice* out);
+int  psgpu_gui_download_weld(psgpu_gui* g, float* pos, float* nrm, float* col4, uint32_t* tris,
+                             uint32_t* vertexMap);
+int  psgpu_gui_weld_times(psgpu_gui* g, float* ms, int maxPhases, const char** names);
+int  psgpu_gui_weld_shells(psgpu_gui* g, PsShellsInfo* info);
+int  psgpu_gui_weld_shells_device(psgpu_gui* g, PsShellsDevice* out);
+int  psgpu_gui_download_weld_shells(psgpu_gui* g, PsShell* shells, uint32_t capacity, uint32_t* vertexShell,
+                                    uint32_t* triShell);
+int  psgpu_gui_weld_shells_times(psgpu_gui* g, float* ms, int maxPhases, const char** names);
+int  psgpu_gui_weld_filter(psgpu_gui* g, const PsShellFilter* f, const uint8_t* mask, uint32_t maskCount,
+                           PsFilterInfo* info);
+int  psgpu_gui_weld_filter_device(psgpu_gui* g, PsFilterDevice* out);
+int  psgpu_gui_download_weld_filter(psgpu_gui* g, float* pos, float* nrm, float* col4, uint32_t* tris,
+                                    uint32_t* vertexMap, uint32_t* shellMap, PsShell* shells,
+                                    uint32_t shellCapacity);
+int  psgpu_gui_weld_filter_times(psgpu_gui* g, float* ms, int maxPhases, const char** names);
+
 /* COMPACTBLOBTREE::fieldvalue and baseColor at n points (probe; col4 may be NULL).  PCM
  * nodes read the contact state below and never update it. */
 int  psgpu_gui_field_values(psgpu_gui* g, const float* xyz, uint32_t n, float* out, float* col4);
@@ -184,6 +234,9 @@ int  psgpu_gui_set_pcm_state(psgpu_gui* g, const float state[2]);
  * in the world box outside which its field is exactly +0 (bounds through the node
  * matrices, none below warps) -- results are bit-identical either way. */
 #define PSGUI_OPT_CULL          2
+/* PSGUI_OPT_TIMING (0 default): the weld, shells and filter calls below record hipEvent
+ * times for their _times calls (the hot path's PSGPU_OPT_KERNEL_TIMING). */
+#define PSGUI_OPT_TIMING        3
 #define PSGUI_JIT_NONE          0    /* interpreter (no compile requested)               */
 #define PSGUI_JIT_PENDING       1    /* compiling; the interpreter serves                */
 #define PSGUI_JIT_ACTIVE        2    /* the tree's kernels serve                         */

@@ -329,6 +329,58 @@ public:
         return info_.ctTriangles > 0 ? PSGPU_RET_SUCCESS : PSGPU_RET_PARAM_ERROR;
     }
 
+    /* The finished run's mesh welded by lattice-edge identity, the weld's shells and its filter
+     * (psgpu_gui_weld, psgpu_gui_weld_shells, psgpu_gui_weld_filter): SimdPolyGpu's weld(),
+     * weldShells() and weldFilter() for this mesh, with rgba colours (out->col holds 4 floats a
+     * vertex).  After run(); shells after weld(), the filter after weldShells():
+     * PSGPU_RET_PARAM_ERROR otherwise (out is left empty). */
+    int weld(Welded* out) {
+        if (!ok()) return status_;
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Welded();
+        PsWeldInfo info;
+        const int rc = psgpu_gui_weld(g_, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        out->col.resize(size_t(info.ctVertices) * 4);
+        return psgpu_gui_download_weld(g_, out->pos.data(), out->nrm.data(), out->col.data(), out->tris.data(),
+                                       out->vertexMap.data());
+    }
+    int weldDevice(PsWeldDevice* out) { return psgpu_gui_weld_device(g_, out); }
+    int weldShells(Shells* out) {
+        if (!ok()) return status_;
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Shells();
+        PsShellsInfo info;
+        const int rc = psgpu_gui_weld_shells(g_, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        return psgpu_gui_download_weld_shells(g_, out->shells.data(), info.ctShells, out->vertexShell.data(),
+                                              out->triShell.data());
+    }
+    int weldShellsDevice(PsShellsDevice* out) { return psgpu_gui_weld_shells_device(g_, out); }
+    int weldFilter(Filtered* out, const PsShellFilter* f = nullptr, const uint8_t* mask = nullptr,
+                   uint32_t maskCount = 0) {
+        if (!ok()) return status_;
+        if (!out) return PSGPU_RET_PARAM_ERROR;
+        *out = Filtered();
+        PsFilterInfo info;
+        const int rc = psgpu_gui_weld_filter(g_, f, mask, maskCount, &info);
+        if (rc != PSGPU_RET_SUCCESS) return rc;
+        out->resize(info);
+        out->col.resize(size_t(info.ctVertices) * 4);
+        return psgpu_gui_download_weld_filter(g_, out->pos.data(), out->nrm.data(), out->col.data(), out->tris.data(),
+                                              out->vertexMap.data(), out->shellMap.data(), out->shells.data(),
+                                              info.ctShells);
+    }
+    int weldFilterDevice(PsFilterDevice* out) { return psgpu_gui_weld_filter_device(g_, out); }
+    /* (gx, gy, gz, axis) of every vertex of the finished run (psgpu_gui_download_edges). */
+    int vertexEdges(std::vector<uint32_t>& edges4) {
+        if (!ok()) return status_;
+        edges4.assign(size_t(info_.ctVertices) * 4, 0u);
+        return psgpu_gui_download_edges(g_, edges4.data());
+    }
+
 private:
     int download() {
         if (haveMesh_) return PSGPU_RET_SUCCESS;

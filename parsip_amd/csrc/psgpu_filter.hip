@@ -11,7 +11,8 @@
 //                    block, kept vertices | kept triangles << 32
 //   k_weld_scan      (psgpu_weld.hip) twice: the shells' block counts, the mesh's
 //   k_filter_emit    one lane per welded vertex: vertexMap (block_rank + block base), the kept
-//                    pos / nrm / col compacted through LDS (compact3)
+//                    pos / nrm / col compacted through LDS (compact3); k_filter_emit<4>, the
+//                    compat context's rgba colours: one 16-byte load and store a kept vertex
 //   k_filter_shells  one lane per shell: shellMap, the kept PsShell records with firstVertex
 //                    through vertexMap; the totals into the control words
 //   k_filter_tris    one lane per triangle: the kept ones compacted in order as vertexMap[tris]
@@ -97,6 +98,7 @@ __global__ void __launch_bounds__(kMeshBlock) k_filter_flags(FilterParams q) {
     if (threadIdx.x == 0) q.blockCnt[blockIdx.x] = (uint64_t)nv | (uint64_t)nt << 32;
 }
 
+template <int W>  // floats a colour (WeldState::colW)
 __global__ void __launch_bounds__(kMeshBlock) k_filter_emit(FilterParams q) {
     __shared__ __attribute__((aligned(16))) uint32_t sIn[3 * kMeshBlock];
     __shared__ uint32_t sOut[3 * kMeshBlock];
@@ -112,7 +114,12 @@ __global__ void __launch_bounds__(kMeshBlock) k_filter_emit(FilterParams q) {
     if (nKept == 0u) return;  // block-uniform
     compact3(q.pos, q.fpos, v0, n, kept, at, nKept, base, sIn, sOut);
     compact3(q.nrm, q.fnrm, v0, n, kept, at, nKept, base, sIn, sOut);
-    compact3(q.col, q.fcol, v0, n, kept, at, nKept, base, sIn, sOut);
+    if constexpr (W == 3) {
+        compact3(q.col, q.fcol, v0, n, kept, at, nKept, base, sIn, sOut);
+    } else {
+        static_assert(W == 4, "rgb or rgba");
+        if (kept) reinterpret_cast<float4*>(q.fcol)[base + at] = reinterpret_cast<const float4*>(q.col)[v];
+    }
 }
 
 // after k_filter_emit: firstVertex goes through vertexMap (a kept shell's vertices are kept)
@@ -203,7 +210,7 @@ int filter_run(WeldState& W, hipStream_t s, bool timed, const PsShellFilter* f, 
     PSGPU_CHECK(F.ctl.reserve((size_t)kCtlWords, H));
     PSGPU_CHECK(F.pos.reserve((size_t)V * 3, H));
     PSGPU_CHECK(F.nrm.reserve((size_t)V * 3, H));
-    PSGPU_CHECK(F.col.reserve((size_t)V * 3, H));
+    PSGPU_CHECK(F.col.reserve((size_t)V * W.colW, H));
     PSGPU_CHECK(F.tris.reserve((size_t)T * 3, H));
     PSGPU_CHECK(F.vertexMap.reserve((size_t)V, H));
     PSGPU_CHECK(F.shellMap.reserve((size_t)S, H));
@@ -244,7 +251,10 @@ int filter_run(WeldState& W, hipStream_t s, bool timed, const PsShellFilter* f, 
     weld_scan_blocks(F.shellCnt, shellBlocks, s);
     weld_scan_blocks(F.blockCnt, blocks, s);
     PSGPU_CHECK(mark());
-    hipLaunchKernelGGL(k_filter_emit, dim3(mesh_blocks(V)), blk, 0, s, q);
+    if (W.colW == 4)
+        hipLaunchKernelGGL(k_filter_emit<4>, dim3(mesh_blocks(V)), blk, 0, s, q);
+    else
+        hipLaunchKernelGGL(k_filter_emit<3>, dim3(mesh_blocks(V)), blk, 0, s, q);
     PSGPU_CHECK(mark());
     hipLaunchKernelGGL(k_filter_shells, dim3(shellBlocks), blk, 0, s, q);
     PSGPU_CHECK(mark());
@@ -287,7 +297,7 @@ int filter_download(const WeldState& W, float* pos, float* nrm, float* col, uint
     if (shells && shellCapacity < S) return PSGPU_RET_PARAM_ERROR;
     PSGPU_CHECK(download_if(pos, F.pos, V, 12));
     PSGPU_CHECK(download_if(nrm, F.nrm, V, 12));
-    PSGPU_CHECK(download_if(col, F.col, V, 12));
+    PSGPU_CHECK(download_if(col, F.col, V, 4 * W.colW));
     PSGPU_CHECK(download_if(tris, F.tris, T, 12));
     PSGPU_CHECK(download_if(vertexMap, F.vertexMap, I.ctInputVertices, 4));
     PSGPU_CHECK(download_if(shellMap, F.shellMap, I.ctInputShells, 4));

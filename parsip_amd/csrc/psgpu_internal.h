@@ -79,6 +79,8 @@ struct WeldState {
     DevBuf<float> nrm;
     DevBuf<float> col;
     DevBuf<uint32_t> tris;
+    uint32_t colW = 3;               // floats a colour: 3 (rgb), or 4 for the compat context's rgba (psgpu_gui.hip);
+                                     // the filter's colours beside it have the same width
     uint64_t doneSeq = ~0ull;        // psgpu_ctx::runSeq of the run the buffers hold the weld of
     PsWeldInfo info{};
     PhaseTimes<kWeldPhases> times;    // a context's weld (a group times its own phases)
@@ -210,7 +212,7 @@ int weld_edges(psgpu_ctx* c, uint64_t* edge, hipStream_t s);
 // One weld in three steps (its device current): a context's (psgpu_weld: `records`' vertex records
 // name the edges) or a group's (psgpu_group_weld: the gathered mesh, its edge ids in edge[0 .. V)).
 struct WeldInput {
-    const float *pos, *nrm, *col;
+    const float *pos, *nrm, *col;  // col: W.colW floats a vertex
     const uint32_t* tris;
     uint32_t V, T;
     const uint64_t* edge;
@@ -228,6 +230,7 @@ int weld_end(WeldState& W, hipStream_t s, uint64_t seq, PsWeldInfo* info);
 // (the callers check that W holds one; for the download its device is current).
 int weld_device(const WeldState& W, PsWeldDevice* out);
 int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap);
+int weld_times(const WeldState& W, float* ms, int maxPhases, const char** names);
 // k_weld_scan on its own: blockCnt[0 .. blocks) becomes its exclusive scan, blockCnt[blocks] the
 // total (both 32-bit halves of a word are scanned), enqueued on s.
 void weld_scan_blocks(uint64_t* blockCnt, uint32_t blocks, hipStream_t s);

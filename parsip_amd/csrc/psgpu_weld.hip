@@ -19,7 +19,8 @@
 //   k_weld_scan     one block: exclusive scan of the block counts, the totals
 //   k_weld_emit     one lane per vertex: the kept vertices' welded ids (block_rank + base),
 //                   their pos / nrm / col compacted through LDS (compact3: 16-byte loads,
-//                   coalesced stores)
+//                   coalesced stores); k_weld_emit<4>, the compat context's rgba colours
+//                   (psgpu_gui.hip): one 16-byte load and store a kept vertex
 //   k_weld_map      vertexMap[gi] = id[rep[gi]] and tris = id[rep[tris]], 16 bytes a lane
 //
 // A group's parts (psgpu_group_weld, psgpu_group.cpp) weld in the gathered mesh's global index
@@ -148,6 +149,7 @@ __global__ void __launch_bounds__(kMeshBlock) k_weld_scan(uint64_t* blockCnt, ui
     if (threadIdx.x == 0) blockCnt[blocks] = sCarry;
 }
 
+template <int W>  // floats a colour
 __global__ void __launch_bounds__(kMeshBlock) k_weld_emit(WeldParams q) {
     __shared__ __attribute__((aligned(16))) uint32_t sIn[3 * kMeshBlock];
     __shared__ uint32_t sOut[3 * kMeshBlock];
@@ -162,7 +164,12 @@ __global__ void __launch_bounds__(kMeshBlock) k_weld_emit(WeldParams q) {
     if (kept) q.kid[gi] = base + at;
     compact3(q.pos, q.wpos, v0, n, kept, at, nKept, base, sIn, sOut);
     compact3(q.nrm, q.wnrm, v0, n, kept, at, nKept, base, sIn, sOut);
-    compact3(q.col, q.wcol, v0, n, kept, at, nKept, base, sIn, sOut);
+    if constexpr (W == 3) {
+        compact3(q.col, q.wcol, v0, n, kept, at, nKept, base, sIn, sOut);
+    } else {
+        static_assert(W == 4, "rgb or rgba");
+        if (kept) reinterpret_cast<float4*>(q.wcol)[base + at] = reinterpret_cast<const float4*>(q.col)[gi];
+    }
 }
 
 __device__ __forceinline__ uint32_t weld_id(const WeldParams& q, uint32_t v) {
@@ -234,7 +241,7 @@ int weld_prepare(WeldState& W, uint32_t V, uint32_t T, WeldParams& q, uint32_t* 
     PSGPU_CHECK(W.blockCnt.reserve((size_t)blocks + 1, H));
     PSGPU_CHECK(W.pos.reserve((size_t)V * 3, H));
     PSGPU_CHECK(W.nrm.reserve((size_t)V * 3, H));
-    PSGPU_CHECK(W.col.reserve((size_t)V * 3, H));
+    PSGPU_CHECK(W.col.reserve((size_t)V * W.colW, H));
     PSGPU_CHECK(W.tris.reserve((size_t)T * 3 + 4, H));
     q.V = V;
     q.T = T;
@@ -304,10 +311,14 @@ int weld_download(const WeldState& W, float* pos, float* nrm, float* col, uint32
     const size_t V = W.info.ctVertices, T = W.info.ctTriangles, Vin = W.info.ctInputVertices;
     PSGPU_CHECK(download_if(pos, W.pos, V, 12));
     PSGPU_CHECK(download_if(nrm, W.nrm, V, 12));
-    PSGPU_CHECK(download_if(col, W.col, V, 12));
+    PSGPU_CHECK(download_if(col, W.col, V, 4 * W.colW));
     PSGPU_CHECK(download_if(tris, W.tris, T, 12));
     PSGPU_CHECK(download_if(vertexMap, W.map, Vin, 4));
     return PSGPU_RET_SUCCESS;
+}
+
+int weld_times(const WeldState& W, float* ms, int maxPhases, const char** names) {
+    return W.times.report(ms, maxPhases, names, kWeldPhaseNames);
 }
 
 bool weld_begin(WeldState& W, uint32_t V, uint32_t T, uint64_t seq, PsWeldInfo* info) {
@@ -350,7 +361,10 @@ int weld_enqueue(WeldState& W, const WeldInput& in, hipStream_t s, PhaseCursor m
     PSGPU_CHECK(marks.mark(s));
     hipLaunchKernelGGL(k_weld_scan, dim3(1), blk, 0, s, q.blockCnt, q.blocks);
     PSGPU_CHECK(marks.mark(s));
-    hipLaunchKernelGGL(k_weld_emit, dim3(q.blocks), blk, 0, s, q);
+    if (W.colW == 4)
+        hipLaunchKernelGGL(k_weld_emit<4>, dim3(q.blocks), blk, 0, s, q);
+    else
+        hipLaunchKernelGGL(k_weld_emit<3>, dim3(q.blocks), blk, 0, s, q);
     PSGPU_CHECK(marks.mark(s));
     hipLaunchKernelGGL(k_weld_map, dim3(q.mapBlocks + triBlocks), blk, 0, s, q);
     PSGPU_CHECK(marks.mark(s));
@@ -405,7 +419,7 @@ int psgpu_download_weld(psgpu_ctx* c, float* pos, float* nrm, float* col, uint32
 }
 
 int psgpu_weld_times(psgpu_ctx* c, float* ms, int maxPhases, const char** names) {
-    return c ? c->weld.times.report(ms, maxPhases, names, kWeldPhaseNames) : 0;
+    return c ? weld_times(c->weld, ms, maxPhases, names) : 0;
 }
 
 }  // extern "C"

@@ -423,15 +423,16 @@ def _weld_shells(L, handle, prefix: str) -> meshio.Shells:
     return meshio.Shells(shells, np.frombuffer(bytes(info), meshio.SHELLS_INFO_DTYPE).copy().reshape(()), vs, ts)
 
 
-def _weld_filter(L, handle, prefix: str, criteria, mask) -> meshio.FilteredMesh:
-    """psgpu_weld_filter / psgpu_group_weld_filter and the download, as meshio.filter_shells returns them."""
+def _weld_filter(L, handle, prefix: str, criteria, mask, col_width: int = 3) -> meshio.FilteredMesh:
+    """psgpu_weld_filter / psgpu_group_weld_filter / psgpu_gui_weld_filter (col_width 4: rgba) and
+    the download, as meshio.filter_shells returns them."""
     c = meshio.shell_filter(criteria)
     m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
     info = PsFilterInfo()
     _check(getattr(L, prefix + "weld_filter")(handle, c.ctypes.data, None if m is None else m.ctypes.data,
                                               0 if m is None else m.size, ctypes.byref(info)), prefix + "weld_filter")
     V, T = info.ctVertices, info.ctTriangles
-    pos, nrm, col = (np.zeros((V, 3), np.float32) for _ in range(3))
+    pos, nrm, col = (np.zeros((V, w), np.float32) for w in (3, 3, col_width))
     tris = np.zeros((T, 3), np.uint32)
     vmap = np.zeros(info.ctInputVertices, np.uint32)
     smap = np.zeros(info.ctInputShells, np.uint32)

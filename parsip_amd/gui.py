@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import blobtree as bt
-from . import gpu
+from . import gpu, meshio
 
 B = bt.BlobNodeType
 _F = np.float32
@@ -251,9 +251,23 @@ _SIG = {
     "psgpu_gui_cull_boxes": (["vp", "u32", "vp", "u32", "vp", "u32", "vp", "u32", "vp", "vp"], "i32"),
     "psgpu_gui_get_pcm_state": (["vp", "vp"], "i32"),
     "psgpu_gui_set_pcm_state": (["vp", "vp"], "i32"),
+    "psgpu_gui_download_edges": (["vp", "vp"], "i32"),
+    "psgpu_gui_weld": (["vp", "pweld"], "i32"),
+    "psgpu_gui_weld_device": (["vp", "pwelddev"], "i32"),
+    "psgpu_gui_download_weld": (["vp", "vp", "vp", "vp", "vp", "vp"], "i32"),
+    "psgpu_gui_weld_times": (["vp", "vp", "i32", "vp"], "i32"),
+    "psgpu_gui_weld_shells": (["vp", "pshells"], "i32"),
+    "psgpu_gui_weld_shells_device": (["vp", "pshellsdev"], "i32"),
+    "psgpu_gui_download_weld_shells": (["vp", "vp", "u32", "vp", "vp"], "i32"),
+    "psgpu_gui_weld_shells_times": (["vp", "vp", "i32", "vp"], "i32"),
+    "psgpu_gui_weld_filter": (["vp", "vp", "vp", "u32", "pfilter"], "i32"),
+    "psgpu_gui_weld_filter_device": (["vp", "pfilterdev"], "i32"),
+    "psgpu_gui_download_weld_filter": (["vp", "vp", "vp", "vp", "vp", "vp", "vp", "vp", "u32"], "i32"),
+    "psgpu_gui_weld_filter_times": (["vp", "vp", "i32", "vp"], "i32"),
 }
 OPT_JIT = 1
 OPT_CULL = 2
+OPT_TIMING = 3
 JIT_NONE, JIT_PENDING, JIT_ACTIVE, JIT_FAILED = 0, 1, 2, 3
 EXPORTED_SYMBOLS = list(_SIG)
 
@@ -263,7 +277,10 @@ def _lib():
     if not getattr(L, "_gui_bound", False):
         T = {"i32": ctypes.c_int, "u32": ctypes.c_uint32, "f32": ctypes.c_float, "vp": ctypes.c_void_p,
              "pvp": ctypes.POINTER(ctypes.c_void_p), "pinfo": ctypes.POINTER(PsGuiInfo), "size": ctypes.c_size_t,
-             "long": ctypes.c_long, None: None}
+             "long": ctypes.c_long, None: None,
+             "pweld": ctypes.POINTER(gpu.PsWeldInfo), "pwelddev": ctypes.POINTER(gpu.PsWeldDevice),
+             "pshells": ctypes.POINTER(gpu.PsShellsInfo), "pshellsdev": ctypes.POINTER(gpu.PsShellsDevice),
+             "pfilter": ctypes.POINTER(gpu.PsFilterInfo), "pfilterdev": ctypes.POINTER(gpu.PsFilterDevice)}
         for name, (args, res) in _SIG.items():
             fn = getattr(L, name)
             fn.argtypes = [T[a] for a in args]
@@ -294,6 +311,102 @@ def cull_boxes(tree: "CompactTree"):
     gpu._check(L.psgpu_gui_cull_boxes(*p, pb.ctypes.data, ob.ctypes.data), "psgpu_gui_cull_boxes")
     box = lambda a: np.stack([a[:, 0:3], a[:, 4:7]], axis=1)  # noqa: E731
     return box(pb[:p[1]]), box(ob[:p[3]])
+
+
+# Edge e of a cell: its lower corner (bits i j k) and axis (psgpu_gui_device.h kCorner1, kAxisOf)
+_EDGE_CORNER1 = (0, 2, 0, 1, 4, 6, 4, 5, 0, 1, 2, 3)
+_EDGE_AXIS = (2, 2, 1, 1, 2, 2, 1, 1, 0, 0, 0, 0)
+
+
+def mpu_vertex_edges(fv, iso: float = ISO_VALUE) -> np.ndarray:
+    """The local lattice edges (ci, cj, ck, axis) of one MPU's vertices in creation order,
+    (n, 4) int64, from its 8 x 8 x 8 corner field values (corner (i, j, k) at ``fv[i, j, k]``).
+    Host only; the rule of the device's k_gui_edges: cells in loop order (i * 7 + j) * 7 + k, a
+    cell's configuration from ``f > iso`` (0 and 255 have no surface), its triangle-table row
+    walked in order keeping each cell edge's first occurrence, and a vertex made only by the
+    edge's owning cell: along each off-axis direction the cell on the edge's lower side,
+    unless the edge lies on the MPU's lower face."""
+    f = np.ascontiguousarray(fv, np.float32).reshape(GRID_DIM, GRID_DIM, GRID_DIM)
+    inside = f > np.float32(iso)
+    n = GRID_DIM - 1
+    cfg = np.zeros((n, n, n), np.int64)
+    for c in range(8):
+        di, dj, dk = (c >> 2) & 1, (c >> 1) & 1, c & 1
+        cfg |= inside[di:di + n, dj:dj + n, dk:dk + n].astype(np.int64) << c
+    tri = gpu.tritable()
+    out = []
+    for cell in np.flatnonzero((cfg != 0) & (cfg != 255)):
+        i, j, k = int(cell) // (n * n), (int(cell) // n) % n, int(cell) % n
+        seen = set()
+        for e in tri[cfg[i, j, k]]:
+            e = int(e)
+            if e < 0:
+                break
+            if e in seen:
+                continue
+            seen.add(e)
+            c1, a = _EDGE_CORNER1[e], _EDGE_AXIS[e]
+            di, dj, dk = (c1 >> 2) & 1, (c1 >> 1) & 1, c1 & 1
+            oi, oj, ok = di == 1 or i == 0, dj == 1 or j == 0, dk == 1 or k == 0
+            if (oj and ok) if a == 0 else (oi and ok) if a == 1 else (oi and oj):
+                out.append((i + di, j + dj, k + dk, a))
+    return np.array(out, np.int64).reshape(-1, 4)
+
+
+def lattice_edges(mesh: "GuiMesh", dims, lo, cellsize: float, iso: float, field) -> np.ndarray:
+    """The global lattice edge (gx, gy, gz, axis) of every vertex of a compat mesh, (V, 4) int64:
+    the host form of ``ParsipOptimized.vertex_edges()``.  Positions do not name a compat
+    vertex's edge (the Newton root leaves it), so the edges are made again from the field:
+    ``field`` maps (n, 3) float32 points to their values (``ParsipOptimized.field_values``'s
+    first result, or the oracle's), ``dims`` is the MPU lattice over the box from ``lo`` at
+    ``cellsize``, ``iso`` the run's iso value.  Every MPU with vertices has its 512 corners
+    evaluated at the device's points (``lo + float(i) * (7 * cs)``, then ``+ cs * float(c)``,
+    in float32, each product rounded once) and its vertices named by `mpu_vertex_edges`; MPU
+    (i, j, k) turns local (ci, cj, ck) into (7 i + ci, 7 j + cj, 7 k + ck).  ValueError when an
+    MPU's count differs from ``mesh.mpu_v``: the field or the lattice is not the run's."""
+    dims = [int(d) for d in dims]
+    n = dims[0] * dims[1] * dims[2]
+    mpu_v = np.asarray(mesh.mpu_v, np.int64)
+    V = len(mesh.pos)
+    if len(mpu_v) != n + 1 or int(mpu_v[-1]) != V:
+        raise ValueError(f"mpu_v has {len(mpu_v)} entries ending at {int(mpu_v[-1]) if len(mpu_v) else 0}: "
+                         f"the lattice has {n} MPUs, the mesh {V} vertices")
+    out = np.zeros((V, 4), np.int64)
+    live = np.flatnonzero(np.diff(mpu_v) > 0)  # an MPU without vertices names none
+    if len(live) == 0:
+        return out
+    lo = np.ascontiguousarray(lo, np.float32)[:3]
+    cs = _F(cellsize)
+    side = _F(GRID_DIM - 1) * cs
+    ijk = np.stack([live // (dims[2] * dims[1]), (live // dims[2]) % dims[1], live % dims[2]], axis=1)
+    org = lo[None, :] + ijk.astype(np.float32) * side                # (L, 3)
+    steps = cs * np.arange(GRID_DIM, dtype=np.float32)               # cs * float(c)
+    pts = np.zeros((len(live), GRID_DIM, GRID_DIM, GRID_DIM, 3), np.float32)
+    pts[..., 0] = (org[:, 0, None] + steps[None, :])[:, :, None, None]
+    pts[..., 1] = (org[:, 1, None] + steps[None, :])[:, None, :, None]
+    pts[..., 2] = (org[:, 2, None] + steps[None, :])[:, None, None, :]
+    fv = np.asarray(field(pts.reshape(-1, 3)), np.float32).reshape(len(live), GRID_DIM, GRID_DIM, GRID_DIM)
+    for r, m in enumerate(live):
+        e = mpu_vertex_edges(fv[r], iso)
+        v0, v1 = int(mpu_v[m]), int(mpu_v[m + 1])
+        if len(e) != v1 - v0:
+            raise ValueError(f"MPU {int(m)} has {v1 - v0} vertices, the field gives {len(e)}")
+        out[v0:v1, :3] = 7 * ijk[r][None, :] + e[:, :3]
+        out[v0:v1, 3] = e[:, 3]
+    return out
+
+
+@dataclass
+class GuiWeldedMesh:
+    """The finished compat run's mesh welded by lattice-edge identity (psgpu_gui_weld): one
+    vertex per lattice edge, in first-occurrence order, with the first occurrence's attributes."""
+
+    pos: np.ndarray         # (Vw, 3) f32
+    nrm: np.ndarray         # (Vw, 3) f32
+    col: np.ndarray         # (Vw, 4) f32 rgba
+    tris: np.ndarray        # (T, 3) u32 welded vertex ids, the run's triangle order
+    vertex_map: np.ndarray  # (V,) u32: welded id of every input vertex
+    info: gpu.PsWeldInfo
 
 
 class ParsipOptimized:
@@ -400,6 +513,74 @@ class ParsipOptimized:
                    "psgpu_gui_download")
         return GuiMesh(pos, nrm, col, tris, (off & 0xFFFFFFFF).astype(np.int64), (off >> 32).astype(np.int64),
                        st[:N])
+
+    def vertex_edges(self) -> np.ndarray:
+        """psgpu_gui_download_edges: the global lattice edge (gx, gy, gz, axis) of every vertex
+        of the finished run, (V, 4) uint32; the host form is `lattice_edges`."""
+        e = np.zeros((self.finish().ctVertices, 4), np.uint32)
+        gpu._check(self._L.psgpu_gui_download_edges(self._g, e.ctypes.data), "psgpu_gui_download_edges")
+        return e
+
+    def set_timing(self, on: bool = True) -> None:
+        """OPT_TIMING: the weld, shells and filter calls record hipEvent times."""
+        gpu._check(self._L.psgpu_gui_set_option(self._g, OPT_TIMING, int(bool(on))), "psgpu_gui_set_option")
+
+    def weld_info(self) -> gpu.PsWeldInfo:
+        """psgpu_gui_weld on the finished run (``finish()`` or ``run()`` first): the welded mesh
+        stays in HBM (``weld_device()``); returns its counts."""
+        info = gpu.PsWeldInfo()
+        gpu._check(self._L.psgpu_gui_weld(self._g, ctypes.byref(info)), "psgpu_gui_weld")
+        return info
+
+    def weld(self) -> GuiWeldedMesh:
+        """Weld the finished run on the device and download the indexed mesh: the same bytes as
+        ``meshio.weld_by_edges(exportMesh(), vertex_edges())``."""
+        info = self.weld_info()
+        V, T, Vin = info.ctVertices, info.ctTriangles, info.ctInputVertices
+        pos = np.zeros((V, 3), np.float32)
+        nrm = np.zeros((V, 3), np.float32)
+        col = np.zeros((V, 4), np.float32)
+        tris = np.zeros((T, 3), np.uint32)
+        vmap = np.zeros(Vin, np.uint32)
+        gpu._check(self._L.psgpu_gui_download_weld(self._g, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data,
+                                                   tris.ctypes.data, vmap.ctypes.data), "psgpu_gui_download_weld")
+        return GuiWeldedMesh(pos, nrm, col, tris, vmap, info)
+
+    def weld_device(self) -> gpu.PsWeldDevice:
+        """Device pointers of the last weld of the current run (``col``: rgba)."""
+        d = gpu.PsWeldDevice()
+        gpu._check(self._L.psgpu_gui_weld_device(self._g, ctypes.byref(d)), "psgpu_gui_weld_device")
+        return d
+
+    def weld_times(self) -> dict:
+        """hipEvent times (ms) of the last weld (OPT_TIMING): the weld's phases, then k_gui_weld_edges."""
+        return gpu._shells_times(self._L.psgpu_gui_weld_times, self._g)
+
+    def weld_shells(self) -> meshio.Shells:
+        """psgpu_gui_weld_shells on the current weld: the same bytes as ``meshio.shells`` of
+        the weld's download."""
+        return gpu._weld_shells(self._L, self._g, "psgpu_gui_")
+
+    def weld_shells_device(self) -> gpu.PsShellsDevice:
+        d = gpu.PsShellsDevice()
+        gpu._check(self._L.psgpu_gui_weld_shells_device(self._g, ctypes.byref(d)), "psgpu_gui_weld_shells_device")
+        return d
+
+    def weld_shells_times(self) -> dict:
+        return gpu._shells_times(self._L.psgpu_gui_weld_shells_times, self._g)
+
+    def weld_filter(self, criteria=None, mask=None) -> meshio.FilteredMesh:
+        """psgpu_gui_weld_filter on the current shells (``weld_shells()`` first): the same bytes
+        as ``meshio.filter_shells`` of the weld's and the shells' downloads (rgba colours)."""
+        return gpu._weld_filter(self._L, self._g, "psgpu_gui_", criteria, mask, col_width=4)
+
+    def weld_filter_device(self) -> gpu.PsFilterDevice:
+        d = gpu.PsFilterDevice()
+        gpu._check(self._L.psgpu_gui_weld_filter_device(self._g, ctypes.byref(d)), "psgpu_gui_weld_filter_device")
+        return d
+
+    def weld_filter_times(self) -> dict:
+        return gpu._shells_times(self._L.psgpu_gui_weld_filter_times, self._g)
 
     @property
     def pcm_state(self) -> np.ndarray:

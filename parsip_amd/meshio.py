@@ -14,6 +14,8 @@ vertex_indices", written in stream order).  Here:
 * `weld_lattice` merges them by the lattice edge each vertex sits on instead (exact for every
   cell size: neighbouring MPUs round a shared corner differently, DESIGN.md §6 "Weld"); the
   device form is `gpu.Polygonizer.weld`;
+* `weld_by_edges` is that weld for edges the caller names (the compat mode's mesh, whose
+  positions do not tell them: `gui.lattice_edges`);
 * `write_off`, `write_ply` follow CMeshVV::save's text layouts; `write_obj` adds the
   common OBJ form with normals (v / vn / f a//a b//b c//c).
 """
@@ -151,13 +153,31 @@ def weld_lattice(mesh, vertex_offsets, cellsize: float, lo, hi, mpu_begin: int =
     id of input vertex v and the triangles are ``vertex_map[mesh.tris]`` (none drops: an MPU has
     one vertex per edge).  Seams towards MPUs outside the range stay open.  The device form is
     ``gpu.Polygonizer.weld`` (same bytes)."""
+    g = lattice_edges(mesh, vertex_offsets, cellsize, lo, hi, mpu_begin)
+    if len(g) and max(soa.mpu_dims(cellsize, lo, hi)) * 7 >= 1 << 20:  # the device's limit too (psgpu_weld)
+        raise ValueError("lattice too large for the edge key")
+    return weld_by_edges(mesh, g)
+
+
+def weld_by_edges(mesh, edges):
+    """Merge the vertices with equal lattice edges; returns ``(TriMesh, vertex_map)``.
+
+    ``edges`` names the global lattice edge (gx, gy, gz, axis) of every vertex of ``mesh``,
+    (V, 4) (`lattice_edges` for a hot-path mesh, ``gui.lattice_edges`` or
+    ``gui.ParsipOptimized.vertex_edges()`` for a compat mesh).  Welded vertices are ordered by
+    their first occurrence and take its position, normal and colour (of any width) bit for bit,
+    ``vertex_map[v]`` is the welded id of input vertex v, the triangles are
+    ``vertex_map[mesh.tris]`` and none drops.  It is the weld inside `weld_lattice`, and the
+    host form of ``gui.ParsipOptimized.weld`` (same bytes)."""
     pos = np.ascontiguousarray(mesh.pos, np.float32).reshape(-1, 3)
     tris_in = np.asarray(mesh.tris).astype(np.int64)
-    g = lattice_edges(mesh, vertex_offsets, cellsize, lo, hi, mpu_begin)
+    g = np.asarray(edges).astype(np.int64).reshape(-1, 4)
+    if len(g) != len(pos):
+        raise ValueError(f"{len(g)} edges for {len(pos)} vertices")
     if len(pos) == 0:
         return TriMesh(pos, tris_in, mesh.nrm, mesh.col), np.zeros(0, np.int64)
-    if max(soa.mpu_dims(cellsize, lo, hi)) * 7 >= 1 << 20:  # the device's limit too (psgpu_weld)
-        raise ValueError("lattice too large for the edge key")
+    if g.min() < 0 or g[:, :3].max() >= 1 << 20 or g[:, 3].max() > 2:
+        raise ValueError("an edge does not fit the edge key (20 bits a coordinate, axis 0..2)")
     key = (((g[:, 0] << 20 | g[:, 1]) << 20 | g[:, 2]) << 2) | g[:, 3]
     _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
     order = np.argsort(first)
@@ -429,7 +449,8 @@ def filter_shells(pos, nrm, col, tris, shells: Shells, criteria=None, mask=None)
     unfiltered mesh."""
     p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
     n = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
-    c = np.ascontiguousarray(col, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(col, np.float32)
+    c = c.reshape(-1, c.shape[-1] if c.ndim > 1 else 3)  # rgb, or the compat mode's rgba rows
     t = np.asarray(tris).astype(np.int64).reshape(-1, 3)
     if not (len(n) == len(c) == len(p) == len(shells.vertex_shell)) or len(t) != len(shells.tri_shell):
         raise ValueError("the shells are not those of this mesh")
