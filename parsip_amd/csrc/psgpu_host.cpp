@@ -3,287 +3,31 @@
 // Host side of PS::SIMDPOLY::Polygonize (PS_Polygonizer.cpp:315-385): MPU lattice,
 // model upload (the reference's per-thread FieldComputer copy, :22-50, becomes one
 // 28 KB device image read through the scalar cache), kernel sequencing on one HIP
-// stream, and the exports back to the reference PolyMPUs layout.
+// stream, the verdict on each finished run and the diagnostic downloads.  What needs no GPU is
+// decided elsewhere: the model image in psgpu_model_build.h, a run's launch shape and its verdict
+// in psgpu_plan.h; the blocking export back to the reference's PolyMPUs is psgpu_export.cpp.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <algorithm>
-#include <numeric>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <functional>
-#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/parsip_gpu.h"
 #include "psgpu_internal.h"
 #include "psgpu_launch.h"
-
+#include "psgpu_model_build.h"
 
 using namespace psgpu;
 
 namespace {
-
-// ---------------------------------------------------------------------------
-// Walk program: the reference's processing order of fieldValue's explicit stack.
-bool op_needs_left(int t) { return (t >= 14 && t <= 19) || (t >= 22 && t <= 25); }
-bool op_needs_right(int t) { return t >= 14 && t <= 19; }
-
-struct ProgramBuilder {
-    const PsSoaBlobOps& O;
-    std::vector<Instr> prog;
-    std::vector<uint8_t> seen;
-    int maxSlot = 0;
-    bool ok = true;
-
-    explicit ProgramBuilder(const PsSoaBlobOps& ops) : O(ops), seen(128, 0) {}
-
-    void emit(int op, int depth, int h) {
-        if (!ok) return;
-        if (op < 0 || op >= (int)O.ctOps || seen[op] || depth > 127 || h + 3 >= kMaxSlots) {
-            ok = false;
-            return;
-        }
-        seen[op] = 1;
-        const int kind = O.opChildKind[op];
-        const int L = O.opLeftChild[op], R = O.opRightChild[op];
-        const int type = O.opType[op];
-        size_t enterAt = 0;
-        if (depth > 3) {
-            Instr e{};
-            e.kind = kEnter;
-            e.idx = (uint16_t)op;
-            e.out = (uint8_t)h;
-            enterAt = prog.size();
-            prog.push_back(e);
-        }
-        int next = h, lslot = 0, rslot = 0;
-        if (kind & 1) {  // right op subtree first (pushed last, popped first)
-            emit(R, depth + 1, h);
-            rslot = h;
-            next = h + 1;
-        }
-        if (kind & 2) {
-            emit(L, depth + 1, next);
-            lslot = next;
-            next = next + 1;
-        }
-        if (!ok) return;
-        int freeSlot = next;
-        if (!(kind & 2) && op_needs_left(type)) {
-            if (L >= 128) { ok = false; return; }
-            Instr p{};
-            p.kind = kPrim;
-            p.idx = (uint16_t)L;
-            p.out = (uint8_t)freeSlot;
-            prog.push_back(p);
-            lslot = freeSlot++;
-        }
-        if (!(kind & 1) && op_needs_right(type)) {
-            if (R >= 128) { ok = false; return; }
-            Instr p{};
-            p.kind = kPrim;
-            p.idx = (uint16_t)R;
-            p.out = (uint8_t)freeSlot;
-            prog.push_back(p);
-            rslot = freeSlot++;
-        }
-        maxSlot = std::max(maxSlot, freeSlot);
-        Instr c{};
-        c.kind = kOp;
-        c.type = (uint8_t)type;
-        c.out = (uint8_t)h;
-        c.lslot = (uint8_t)lslot;
-        c.rslot = (uint8_t)rslot;
-        c.childKind = (uint8_t)kind;
-        c.L = (uint8_t)L;
-        c.R = (uint8_t)R;
-        c.idx = (uint16_t)op;
-        prog.push_back(c);
-        if (depth > 3) prog[enterAt].skipTo = (uint16_t)prog.size();
-        if (prog.size() > (size_t)kMaxInstr) ok = false;
-    }
-};
-
-bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
-int build_device_model(const PsSoaBlobPrims& P, const PsSoaPrimMatrices& Mx, const PsSoaBlobOps& O, DevModel& D) {
-    memset(&D, 0, sizeof(D));
-    if (P.ctPrims == 0 || P.ctPrims > 128 || O.ctOps > 128) return PSGPU_RET_PARAM_ERROR;
-    D.ctPrims = P.ctPrims;
-    D.ctOps = O.ctOps;
-    if (O.ctOps == 0) {
-        for (uint32_t i = 0; i < P.ctPrims; ++i) {
-            Instr s{};
-            s.kind = kSumPrim;
-            s.idx = (uint16_t)i;
-            D.instr[i] = s;
-        }
-        D.nInstr = P.ctPrims;
-        D.nSlots = 1;
-    } else {
-        ProgramBuilder b(O);
-        b.emit(0, 0, 0);
-        if (!b.ok) return PSGPU_RET_INVALID_BVH;
-        D.nInstr = (uint32_t)b.prog.size();
-        std::copy(b.prog.begin(), b.prog.end(), D.instr);
-        D.nSlots = (uint32_t)std::max(1, b.maxSlot);
-    }
-    for (uint32_t i = 0; i < 128; ++i) {
-        DevOp& d = D.ops[i];
-        d.lo[0] = O.vBoxLoX[i]; d.lo[1] = O.vBoxLoY[i]; d.lo[2] = O.vBoxLoZ[i];
-        d.hi[0] = O.vBoxHiX[i]; d.hi[1] = O.vBoxHiY[i]; d.hi[2] = O.vBoxHiZ[i];
-        d.resY = O.resY[i];
-        d.type = O.opType[i];
-    }
-    // Colour of each op whose subtree is all +0 fields (culled primitives, or pruned: the
-    // reference's colour pass then reads zeroed arrays, :1472-1522): a constant of the tree
-    // and the primitive colours, computed in fp32 exactly as op_colour_weights + the
-    // weighted sum on the device.  Children first (post-order over the tree the program
-    // builder validated: every child op id < ctOps, every prim id < 128, no cycles), so any
-    // op numbering works, not only pre-order; unreachable ops keep zero.
-    const float* pc[3] = {P.colorX, P.colorY, P.colorZ};
-    std::function<void(int)> zero_col = [&](int op) {
-        const uint32_t t = O.opType[op], kind = O.opChildKind[op];
-        const uint32_t L = O.opLeftChild[op], R = O.opRightChild[op];
-        if (kind & 2) zero_col((int)L);
-        if (kind & 1) zero_col((int)R);
-        float cl[3], cr[3];
-        for (int k = 0; k < 3; ++k) {
-            cl[k] = (kind & 2) ? D.zeroCol[L][k] : pc[k][L];
-            cr[k] = (kind & 1) ? D.zeroCol[R][k] : pc[k][R];
-        }
-        const float lf = 0.0f, rf = 0.0f;
-        float v = 0.0f, wl = 0.0f, wr = 0.0f;
-        bool weighted = true;
-        switch (t) {
-        case PSGPU_OP_BLEND: v = lf + rf; wl = 2.0f * (0.5f + lf) - 1.0f; wr = 2.0f * (0.5f + rf) - 1.0f; break;
-        case PSGPU_OP_UNION: v = lf > rf ? lf : rf; wl = (v - lf) == 0.0f ? 1.0f : 0.0f; wr = (v - rf) == 0.0f ? 1.0f : 0.0f; break;
-        case PSGPU_OP_INTERSECT: v = lf < rf ? lf : rf; wl = (v - lf) == 0.0f ? 1.0f : 0.0f; wr = (v - rf) == 0.0f ? 1.0f : 0.0f; break;
-        case PSGPU_OP_DIF: { const float q = 1.0f - rf; v = lf < q ? lf : q; wl = lf == v ? 1.0f : 0.0f; wr = (1.0f - rf) == v ? 1.0f : 0.0f; } break;
-        case PSGPU_OP_SMOOTHDIF: v = lf * (1.0f - rf); wl = lf == v ? 1.0f : 0.0f; wr = (1.0f - rf) == v ? 1.0f : 0.0f; break;
-        default: weighted = false; break;
-        }
-        for (int k = 0; k < 3; ++k) {
-            if (weighted) D.zeroCol[op][k] = wl * cl[k] + wr * cr[k];
-            else if (t >= PSGPU_OP_WARPTWIST && t <= PSGPU_OP_WARPSHEAR) D.zeroCol[op][k] = cl[k];
-            else D.zeroCol[op][k] = 0.0f;  // not used: zero subtrees contain only the types above
-        }
-    };
-    if (O.ctOps > 0) zero_col(0);
-    // every one of the 128 prim slots is uploaded: the reference evaluates whatever
-    // index an op names, even past ctPrims (SOABlobPrims keeps all 128 entries)
-    for (uint32_t i = 0; i < 128; ++i) {
-        DevPrim& d = D.prims[i];
-        d.pos[0] = P.posX[i]; d.pos[1] = P.posY[i]; d.pos[2] = P.posZ[i];
-        d.dir[0] = P.dirX[i]; d.dir[1] = P.dirY[i]; d.dir[2] = P.dirZ[i];
-        d.res[0] = P.resX[i]; d.res[1] = P.resY[i]; d.res[2] = P.resZ[i];
-        d.col[0] = P.colorX[i]; d.col[1] = P.colorY[i]; d.col[2] = P.colorZ[i];
-        d.type = P.skeletType[i];
-        const uint32_t im = P.idxMatrix[i];
-        d.hasMatrix = im != 0;
-        if (im != 0) {
-            if (im >= 128) return PSGPU_RET_PARAM_ERROR;
-            memcpy(d.mat, &Mx.matrix[im * PSGPU_PRIM_MATRIX_STRIDE], 12 * sizeof(float));
-        }
-        // exact-culling eligibility (see make_cull_mask in psgpu_kernels.hip)
-        bool c = !d.hasMatrix && finite3(d.pos);
-        switch (d.type) {
-        case PSGPU_PRIM_POINT: break;
-        case PSGPU_PRIM_LINE: {
-            const double ux = (double)d.dir[0] - d.pos[0], uy = (double)d.dir[1] - d.pos[1],
-                         uz = (double)d.dir[2] - d.pos[2];
-            c = c && finite3(d.dir) && (ux * ux + uy * uy + uz * uz) > 1e-6;
-        } break;
-        case PSGPU_PRIM_CUBE: c = c && std::isfinite(d.res[0]) && d.res[0] >= 0.0f; break;
-        case PSGPU_PRIM_CYLINDER: {
-            const double n2 = (double)d.dir[0] * d.dir[0] + (double)d.dir[1] * d.dir[1] + (double)d.dir[2] * d.dir[2];
-            c = c && finite3(d.dir) && std::fabs(n2 - 1.0) < 1e-4 && d.res[0] >= 0.0f && d.res[1] >= 0.0f &&
-                std::isfinite(d.res[0]) && std::isfinite(d.res[1]);
-        } break;
-        default: c = false; break;
-        }
-        // culling skeleton (CullSeg, psgpu_model.h): a lower bound of the distance
-        CullSeg& cs = D.cull[i];
-        memset(&cs, 0, sizeof(cs));
-        const float inf = std::numeric_limits<float>::infinity();
-        cs.radius = inf;  // never culled unless eligible below
-        cs.tmin = 0.0f;
-        cs.tmax = 1.0f;
-        cs.axisClear = -inf;
-        cs.boxHalf = inf;  // not an axis-aligned box: no gap form
-        uint32_t flags = c ? 1u : 0u;
-        if (c) {
-            for (int a = 0; a < 3; ++a) cs.a[a] = d.pos[a];
-            cs.radius = 0.0f;
-            double uu = 0.0;
-            if (d.type == PSGPU_PRIM_LINE) {
-                for (int a = 0; a < 3; ++a) cs.u[a] = d.dir[a] - d.pos[a];
-                cs.tmin = -inf;
-                cs.tmax = inf;
-                flags |= 2u;
-            } else if (d.type == PSGPU_PRIM_CYLINDER) {
-                for (int a = 0; a < 3; ++a) cs.u[a] = d.res[1] * d.dir[a];  // axis segment, length h
-                cs.radius = d.res[0];
-                cs.axisClear = 0.05f;
-                flags |= 4u;
-            } else if (d.type == PSGPU_PRIM_CUBE) {
-                cs.radius = (float)(d.res[0] * 1.7320508075688772 * (1.0 + 1e-6));
-                cs.boxHalf = d.res[0];
-            } else {
-                cs.boxHalf = 0.0f;  // Point
-            }
-            for (int a = 0; a < 3; ++a) uu += (double)cs.u[a] * cs.u[a];
-            cs.invUU = uu > 0.0 ? (float)(1.0 / uu) : 0.0f;
-            if (d.type == PSGPU_PRIM_CYLINDER && uu == 0.0) {  // h = 0: no axis direction
-                flags &= ~1u;
-                cs.radius = inf;
-            }
-        } else if (d.type == PSGPU_PRIM_TRIANGLE) {
-            cs.radius = -inf;  // field exactly 0 everywhere (dist2 = FLT_MAX)
-        }
-        if (i >= P.ctPrims) {  // (the culling masks only cover ctPrims)
-            cs.radius = inf;
-            cs.boxHalf = inf;
-        }
-        d.cullable = flags;
-    }
-    // field bounds (k_precheck, prim_bound in psgpu_device.h) need every primitive the
-    // walk evaluates to have a true-distance bound with sane parameters (the culling
-    // eligibility above) or be a Triangle (field 0), and every op a monotone map
-    bool bnd = D.nInstr > 0;
-    for (uint32_t k = 0; k < D.nInstr; ++k) {
-        const Instr& I = D.instr[k];
-        if (I.kind == kOp && !((I.type >= 14 && I.type <= 18) || (I.type >= 22 && I.type <= 25))) bnd = false;
-        if (I.kind == kPrim || I.kind == kSumPrim) {
-            const DevPrim& q = D.prims[I.idx];
-            if (!(q.type == PSGPU_PRIM_TRIANGLE || (q.cullable & 1u))) bnd = false;
-        }
-    }
-    D.boundable = bnd ? 1u : 0u;
-    // the primitives that, all culled over a box, leave the root exactly +0 there (k_sieve)
-    D.rootZeroValid = root_zero_set(D, D.rootZero) ? 1u : 0u;
-    if (!D.rootZeroValid) D.rootZero[0] = D.rootZero[1] = 0ull;
-    return PSGPU_RET_SUCCESS;
-}
-
-void lattice_dims(float cs, const PsVec3f& lo, const PsVec3f& hi, uint32_t d[3]) {
-    const float ext[3] = {hi.x - lo.x, hi.y - lo.y, hi.z - lo.z};
-    for (int a = 0; a < 3; ++a) {
-        const float q = ext[a] / cs;
-        const int cells = (int)std::ceil(q);
-        int n = cells / PSGPU_CELLS_PER_MPU;
-        if (cells % PSGPU_CELLS_PER_MPU != 0) ++n;
-        d[a] = n > 0 ? (uint32_t)n : 0u;
-    }
-}
 
 const char* kKernelNames[kNumKernels] = {"k_precheck", "k_mpu", "k_vertex", "k_finish"};
 
@@ -297,52 +41,39 @@ int hip_fail(hipError_t e, const char* what) {
 }
 
 int set_device(psgpu_ctx* c) { return hip_fail(hipSetDevice(c->device), "hipSetDevice"); }
+
+int finished_run(psgpu_ctx* c, PsMeshInfo* info) {
+    const int rc = psgpu_finish(c, info);  // PARAM_ERROR for a null context
+    return rc == PSGPU_RET_SUCCESS ? set_device(c) : rc;
+}
 }  // namespace psgpu
 
 namespace {
 
-// k_precheck covers the MPU range with 2x2x2 bricks of MPUs (one per wavefront: a
-// compact box for its culling test), whole brick rows along x.
-void brick_layout(const psgpu_ctx* c, uint32_t* i0, uint32_t bd[3]) {
-    const uint32_t nyz = c->dims[1] * c->dims[2];
-    const uint32_t first = nyz ? c->mpuBegin / nyz : 0;
-    const uint32_t last = (nyz && c->mpuCount) ? (c->mpuBegin + c->mpuCount - 1) / nyz : first;
-    *i0 = first / 2;
-    bd[0] = c->mpuCount ? last / 2 - first / 2 + 1 : 0;
-    bd[1] = (c->dims[1] + 1) / 2;
-    bd[2] = (c->dims[2] + 1) / 2;
-}
-// The brick permutation of k_precheck: stride 1 keeps the lattice order; otherwise a
-// stride near n / golden ratio, coprime with n, so consecutive wave slots (one block, one
-// CU) take bricks far apart and the bricks crossed by the surface spread over the chip.
-uint32_t brick_stride(uint32_t n, bool spread) {
-    if (!spread || n < 3) return 1u;
-    for (uint32_t s = (uint32_t)(n * 0.6180339887) | 1u; s > 1; --s)
-        if (std::gcd(s, n) == 1u) return s;
-    return 1u;
-}
-size_t brick_count(const psgpu_ctx* c) {
-    uint32_t i0, bd[3];
-    brick_layout(c, &i0, bd);
-    return (size_t)bd[0] * bd[1] * bd[2];
+// The brick layout of the context's range: computed once per enqueue and handed to what sizes the
+// buffers, plans the run and fills its parameters.
+BrickLayout run_bricks(const psgpu_ctx* c) { return brick_layout(c->dims, c->mpuBegin, c->mpuCount); }
+
+// The context's four capacities as psgpu_plan.h judges and grows them.
+Caps caps_of(const psgpu_ctx* c) { return {c->vcap, c->tcap, c->vShardCap, c->tShardCap}; }
+void set_caps(psgpu_ctx* c, const Caps& k) {
+    c->vcap = k.v;
+    c->tcap = k.t;
+    c->vShardCap = k.shardV;
+    c->tShardCap = k.shardT;
 }
 
-// front_sub_cap (psgpu_plan.h) for both k_precheck grids (2 and 4 bricks per block)
-uint32_t front_cap(size_t bricks) {
-    const uint32_t b = (uint32_t)bricks;
-    return std::max(front_sub_cap((b + 1u) / 2u, 2u), front_sub_cap((b + 3u) / 4u, 4u));
-}
-
-int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
-    const size_t n = std::max<uint32_t>(mpuCount, 1);
-    c->pShardCap = 8u * (uint32_t)((brick_count(c) + kShards - 1) / kShards);
+int ensure_buffers(psgpu_ctx* c, const BrickLayout& bricks) {
+    const size_t n = std::max<uint32_t>(c->mpuCount, 1);
+    const size_t nBricks = brick_count(bricks);
+    c->pShardCap = 8u * (uint32_t)((nBricks + kShards - 1) / kShards);
     // k_front's 8 sub-queues: a block's bricks x 8 MPUs for every 8th k_precheck block
-    const size_t fq = 8 * front_cap(brick_count(c));
+    const size_t fq = 8 * front_cap(nBricks);
     const size_t nq = std::max<size_t>((size_t)c->pShardCap * kShards, fq);
     constexpr Growth H = Growth::ByHalf;
     PSGPU_CHECK(c->pq.reserve(nq, H));
     PSGPU_CHECK(c->pqMask.reserve(nq * 4, H));  // culling + op-inside mask per entry
-    PSGPU_CHECK(c->liveList.reserve(brick_count(c), H));  // k_sieve: at most every brick
+    PSGPU_CHECK(c->liveList.reserve(nBricks, H));  // k_sieve: at most every brick
     bool fresh = false;
     if (fq) PSGPU_CHECK(c->fqReady.reserve(fq, H, &fresh));
     if (fresh)  // ready words start at 0: no run's tag
@@ -364,10 +95,10 @@ int ensure_buffers(psgpu_ctx* c, uint32_t mpuCount) {
 
 // The launch shape of the context's next run (psgpu_plan.h decides it, from these inputs alone).
 // separate: finish re-runs a run whose in-kernel wait gave up, as separate launches.
-LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
+LaunchPlan plan_run(const psgpu_ctx* c, const BrickLayout& bricks, bool separate) {
     PlanInput in{};
     in.numCUs = c->numCUs;
-    in.bricks = brick_count(c);
+    in.bricks = brick_count(bricks);
     in.mpuCount = c->mpuCount;
     in.opt = c->opt;
     in.last = c->last;
@@ -376,9 +107,8 @@ LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
     in.mpuTicks = c->mpuTicksOpt != 0;
     in.splittable = c->splittable;
     // k_sieve: with culling on, a root-zero set, and brick coordinates that fit a list entry
-    uint32_t bi0, bd[3];
-    brick_layout(c, &bi0, bd);
-    in.sievable = c->cull != 0 && c->model.rootZeroValid != 0u && (uint64_t)bi0 + bd[0] <= (1u << 21) &&
+    const uint32_t* bd = bricks.dims;
+    in.sievable = c->cull != 0 && c->model.rootZeroValid != 0u && (uint64_t)bricks.i0 + bd[0] <= (1u << 21) &&
                   bd[1] <= (1u << 21) && bd[2] <= (1u << 21);
     if (const JitKernels* J = c->jit.kernels.get()) {
         in.jit = true;
@@ -393,7 +123,7 @@ LaunchPlan plan_run(const psgpu_ctx* c, bool separate) {
     return plan_launch(in);
 }
 
-Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
+Params make_params(psgpu_ctx* c, const BrickLayout& bricks, const LaunchPlan& plan) {
     Params p;
     memset(&p, 0, sizeof(p));  // padding too: graph replay compares parameter bytes
     p.model = c->dModel;
@@ -409,9 +139,10 @@ Params make_params(psgpu_ctx* c, const LaunchPlan& plan) {
     p.mpuBegin = c->mpuBegin;
     p.mpuCount = c->mpuCount;
     p.cull = (uint32_t)c->cull;
-    brick_layout(c, &p.brickI0, p.brickDims);
+    p.brickI0 = bricks.i0;
+    for (int a = 0; a < 3; ++a) p.brickDims[a] = bricks.dims[a];
     p.preBlocks = plan.preBlocks;
-    p.brickStride = brick_stride((uint32_t)brick_count(c), (c->debug & 16384) != 0);
+    p.brickStride = brick_stride((uint32_t)brick_count(bricks), (c->debug & 16384) != 0);
     p.brickMagic[0] = p.brickDims[2] ? 0xffffffffu / p.brickDims[2] : 0u;
     p.brickMagic[1] = (p.brickDims[2] * p.brickDims[1]) ? 0xffffffffu / (p.brickDims[2] * p.brickDims[1]) : 0u;
     p.sieve = plan.sieve;
@@ -528,29 +259,13 @@ DevCounters empty_counters() {
 // The stamp buffer of `cap` waves a kernel (PSGPU_OPT_STAMPS): 24 bytes a wave per kernel, then 64 a wave.
 size_t stamp_bytes(size_t cap) { return (size_t)kNumStampKernels * cap * 24 + cap * 64; }
 
-// A finished run's counters over its shards: sums, and the largest shard's vertices and triangles.
-struct ShardSums {
-    uint32_t v = 0, t = 0, s = 0, p = 0, b = 0, maxV = 0, maxT = 0;
-    explicit ShardSums(const DevCounters& h) {
-        for (int k = 0; k < kShards; ++k) {
-            v += h.shard[k].v;
-            t += h.shard[k].t;
-            s += h.shard[k].s;
-            p += h.shard[k].p;
-            b += h.shard[k].b;
-            maxV = std::max(maxV, h.shard[k].v);
-            maxT = std::max(maxT, h.shard[k].t);
-        }
-    }
-};
-
 // Enqueue one polygonization: its shape is planned once, here, and kept as c->run.  k_precheck
 // needs nothing reset (k_finish of the previous run reset this run's counters) and k_finish
 // publishes the counters to mapped host memory.  Replayed from a hipGraph (one per counter
 // set) while the kernels, the parameters and the plan repeat, e.g. per frame of an animation.
 // separate: a protocol-error re-run, as separate launches.
 void reset_run_state(psgpu_ctx* c);
-int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
+int enqueue(psgpu_ctx* c, hipStream_t s, const BrickLayout& bricks, bool separate = false) {
     if (c->mpuCount == 0) {  // nothing to launch: an empty result
         c->runTicks = c->mpuTicksOpt != 0;
         *c->hostCtr = empty_counters();
@@ -573,8 +288,8 @@ int enqueue(psgpu_ctx* c, hipStream_t s, bool separate = false) {
     // drain once in 2^32 runs)
     if (c->epochRuns >= 0xffffffffull) reset_run_state(c);
     ++c->epochRuns;
-    const LaunchPlan plan = c->run = plan_run(c, separate);
-    const Params p = make_params(c, plan);
+    const LaunchPlan plan = c->run = plan_run(c, bricks, separate);
+    const Params p = make_params(c, bricks, plan);
     c->runTicks = p.mpuTicks != nullptr;
     c->debug &= ~((1 << 20) | (1 << 25) | (1 << 26) | (1 << 27));  // the short-grid / protocol test hooks apply to one run
     if (p.spans) c->spanNext++;
@@ -752,127 +467,11 @@ int psgpu_mpu_dims(float cellsize, const PsSoaBlobPrims* prims, uint32_t dims[3]
     return PSGPU_RET_SUCCESS;
 }
 
-int psgpu_translate_blobtree_type(int t) {
-    // _constSettings.h:26-38 -> PS_Polygonizer.h:84-91
-    static const int map[29] = {
-        PSGPU_PRIM_POINT, PSGPU_PRIM_LINE, PSGPU_PRIM_CYLINDER, PSGPU_PRIM_DISC, PSGPU_PRIM_RING,
-        PSGPU_PRIM_POLYGON, PSGPU_PRIM_CUBE, PSGPU_PRIM_TRIANGLE, PSGPU_PRIM_CATMULLROM, PSGPU_PRIM_SKELETON,
-        PSGPU_PRIM_QUADRICPOINT, PSGPU_PRIM_HALFPLANE, PSGPU_PRIM_NULL, -1 /* Instance */,
-        PSGPU_OP_UNION, PSGPU_OP_INTERSECT, PSGPU_OP_DIF, PSGPU_OP_SMOOTHDIF, PSGPU_OP_BLEND,
-        PSGPU_OP_RICCIBLEND, PSGPU_OP_GRADIENTBLEND, PSGPU_PRIM_FASTQPS, PSGPU_OP_PCM, PSGPU_OP_CACHE,
-        PSGPU_OP_WARPTWIST, PSGPU_OP_WARPTAPER, PSGPU_OP_WARPBEND, PSGPU_OP_WARPSHEAR, PSGPU_OP_TEXTURE};
-    return (t >= 0 && t < 29) ? map[t] : -1;
-}
+int psgpu_translate_blobtree_type(int t) { return translate_blobtree_type(t); }
 
-// PrepareBBoxes (PS_Polygonizer.cpp:55-309) with iso distance ISO_DIST + 5*MIN_CELL_SIZE.
 int psgpu_prepare_bboxes(float cellsize, PsSoaBlobPrims* P, PsSoaBoxMatrices* BM, PsSoaBlobOps* O) {
     (void)cellsize;
-    if (!P || !O || P->ctPrims == 0 || P->ctPrims > 128) return PSGPU_RET_PARAM_ERROR;
-    const float iso = PSGPU_ISO_DIST + 5.0f * PSGPU_MIN_CELL_SIZE;
-    float* boxLo[3] = {P->vPrimBoxLoX, P->vPrimBoxLoY, P->vPrimBoxLoZ};
-    float* boxHi[3] = {P->vPrimBoxHiX, P->vPrimBoxHiY, P->vPrimBoxHiZ};
-    for (uint32_t i = 0; i < P->ctPrims; ++i) {
-        const float p[3] = {P->posX[i], P->posY[i], P->posZ[i]};
-        const float d[3] = {P->dirX[i], P->dirY[i], P->dirZ[i]};
-        float lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) { lo[a] = boxLo[a][i]; hi[a] = boxHi[a][i]; }
-        switch (P->skeletType[i]) {
-        case PSGPU_PRIM_POINT:
-            for (int a = 0; a < 3; ++a) { lo[a] = p[a] - iso; hi[a] = p[a] + iso; }
-            break;
-        case PSGPU_PRIM_LINE:
-            for (int a = 0; a < 3; ++a) {
-                const float e = iso * 1.0f + (3.0f * iso) * (d[a] - p[a]);
-                lo[a] = p[a] - e; hi[a] = d[a] + e;
-            }
-            break;
-        case PSGPU_PRIM_RING: case PSGPU_PRIM_DISC: {
-            const float r = P->resX[i] + iso;
-            for (int a = 0; a < 3; ++a) {
-                const float e = (r + iso) * (1.0f - d[a]) + iso * d[a];
-                lo[a] = p[a] - e; hi[a] = p[a] + e;
-            }
-        } break;
-        case PSGPU_PRIM_CYLINDER: {
-            const float r = P->resX[i], h = P->resY[i];
-            for (int a = 0; a < 3; ++a) {
-                const float s1 = p[a] + h * d[a];
-                const float e = (iso + r) * 1.0f + (0.5f * iso) * d[a];
-                lo[a] = p[a] - e; hi[a] = s1 + e;
-            }
-        } break;
-        case PSGPU_PRIM_CUBE: {
-            const float s = P->resX[i] + iso;
-            for (int a = 0; a < 3; ++a) { lo[a] = p[a] - s; hi[a] = p[a] + s; }
-        } break;
-        case PSGPU_PRIM_TRIANGLE: {
-            const float r[3] = {P->resX[i], P->resY[i], P->resZ[i]};
-            for (int a = 0; a < 3; ++a) {
-                float mn = p[a] < d[a] ? p[a] : d[a];
-                mn = mn < r[a] ? mn : r[a];
-                float mx = p[a] > d[a] ? p[a] : d[a];
-                mx = mx > r[a] ? mx : r[a];
-                lo[a] = mn - iso; hi[a] = mx + iso;
-            }
-        } break;
-        default: break;
-        }
-        const uint32_t im = P->idxMatrix[i];
-        if (im != 0 && BM && im < BM->count) {  // mat4Transform, PS_MATRIX4.h:199-209 (column vectors)
-            const float* M = &BM->matrix[im * PSGPU_BOX_MATRIX_STRIDE];
-            float tl[3], th[3];
-            for (int r = 0; r < 3; ++r) {
-                tl[r] = ((M[r] * lo[0] + M[4 + r] * lo[1]) + M[8 + r] * lo[2]) + M[12 + r];
-                th[r] = ((M[r] * hi[0] + M[4 + r] * hi[1]) + M[8 + r] * hi[2]) + M[12 + r];
-            }
-            memcpy(lo, tl, sizeof(lo));
-            memcpy(hi, th, sizeof(hi));
-        }
-        for (int a = 0; a < 3; ++a) { boxLo[a][i] = lo[a]; boxHi[a][i] = hi[a]; }
-        float* bl = &P->bboxLo.x;
-        float* bh = &P->bboxHi.x;
-        for (int a = 0; a < 3; ++a) {
-            if (i == 0) { bl[a] = lo[a]; bh[a] = hi[a]; }
-            else { bl[a] = bl[a] < lo[a] ? bl[a] : lo[a]; bh[a] = bh[a] > hi[a] ? bh[a] : hi[a]; }
-        }
-    }
-    if (O->ctOps > 0) {  // op boxes bottom-up (:238-307) as a post-order walk
-        std::vector<uint8_t> done(256, 0);
-        std::vector<uint32_t> st{0};
-        size_t guard = 0;
-        while (!st.empty()) {
-            if (++guard > 100000) return PSGPU_RET_INVALID_BVH;
-            const uint32_t op = st.back();
-            if (op >= 128) return PSGPU_RET_INVALID_BVH;
-            const uint32_t L = O->opLeftChild[op], R = O->opRightChild[op];
-            const int lop = (O->opChildKind[op] & 2) >> 1, rop = O->opChildKind[op] & 1;
-            if ((lop && !done[L]) || (rop && !done[R])) {
-                if (lop && !done[L]) st.push_back(L);
-                if (rop && !done[R]) st.push_back(R);
-                continue;
-            }
-            st.pop_back();
-            auto get = [&](int isOp, uint32_t k, float lo[3], float hi[3]) {
-                if (isOp) {
-                    lo[0] = O->vBoxLoX[k]; lo[1] = O->vBoxLoY[k]; lo[2] = O->vBoxLoZ[k];
-                    hi[0] = O->vBoxHiX[k]; hi[1] = O->vBoxHiY[k]; hi[2] = O->vBoxHiZ[k];
-                } else {
-                    for (int a = 0; a < 3; ++a) { lo[a] = boxLo[a][k]; hi[a] = boxHi[a][k]; }
-                }
-            };
-            float l0[3], h0[3], l1[3], h1[3];
-            get(lop, L, l0, h0);
-            get(rop, R, l1, h1);
-            float* oLo[3] = {O->vBoxLoX, O->vBoxLoY, O->vBoxLoZ};
-            float* oHi[3] = {O->vBoxHiX, O->vBoxHiY, O->vBoxHiZ};
-            for (int a = 0; a < 3; ++a) {
-                oLo[a][op] = l0[a] < l1[a] ? l0[a] : l1[a];
-                oHi[a][op] = h0[a] > h1[a] ? h0[a] : h1[a];
-            }
-            done[op] = 1;
-        }
-    }
-    return PSGPU_RET_SUCCESS;
+    return prepare_bboxes(P, BM, O);
 }
 
 uint64_t psgpu_debug_device_bytes(void) { return g_deviceBytes.load(); }
@@ -979,7 +578,7 @@ int psgpu_set_option(psgpu_ctx* c, int option, int64_t value) {
         // a pending result is dropped with them
         if (c->pending) (void)hipStreamSynchronize(c->runStream);
         set_pending(c, false);
-        c->seenV = c->seenT = c->seenShardV = c->seenShardT = 0;
+        c->seen = Caps{};
         c->vk.release();
         c->vp.release();
         c->tq.release();
@@ -1113,11 +712,9 @@ int psgpu_polygonize(psgpu_ctx* c, float cellsize, uint32_t mpuBegin, uint32_t m
     tier_count(c);
     // capacity from the largest finished run + 1/4 (grows only; finish() still re-runs
     // on an overflow, so a prediction that falls short costs time, never output)
-    c->vcap = std::max(c->vcap, c->seenV + c->seenV / 4);
-    c->tcap = std::max(c->tcap, c->seenT + c->seenT / 4);
-    c->vShardCap = std::max(c->vShardCap, c->seenShardV + c->seenShardV / 4);
-    c->tShardCap = std::max(c->tShardCap, c->seenShardT + c->seenShardT / 4);
-    rc = ensure_buffers(c, c->mpuCount);
+    set_caps(c, grown_ahead(caps_of(c), c->seen));
+    const BrickLayout bricks = run_bricks(c);
+    rc = ensure_buffers(c, bricks);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     // alone: no OTHER context has a run pending on the device (this context's own earlier
     // runs share its stream, so they never overlap this one)
@@ -1130,7 +727,7 @@ int psgpu_polygonize(psgpu_ctx* c, float cellsize, uint32_t mpuBegin, uint32_t m
     // waits end only at their bounds (6-8 engines on a C4 share: protocol errors, ms per step;
     // profiles/r06_engines_waits.txt)
     c->crowded = others >= kMaxWaitingPeers;
-    rc = enqueue(c, s);
+    rc = enqueue(c, s, bricks);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     c->runStream = s;
     set_pending(c, true);
@@ -1146,37 +743,22 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
         if (rc != PSGPU_RET_SUCCESS) return rc;
         PSGPU_CHECK(hipStreamSynchronize(c->runStream));
         set_pending(c, false);
-        // grow and re-run if the work queues or the compact outputs did not fit
+        // judge it (psgpu_plan.h); grow and re-run while the S2 grid, the work queues or the
+        // compact outputs did not fit
+        const DevCounters& h = *c->hostCtr;
+        const BrickLayout bricks = run_bricks(c);
         bool reran = false;
-        for (int attempt = 0; attempt < 4; ++attempt) {
-            const DevCounters& h = *c->hostCtr;
-            const ShardSums sum(h);
-            const uint32_t V = sum.v, T = sum.t, mv = sum.maxV, mt = sum.maxT, Q = sum.p;
-            bool gridShort = c->mpuCount > 0 && Q > c->run.mpb * c->run.mpuBlocks;
-            if (c->run.front) {  // k_front: each sub-queue against its own rows of S2 blocks
-                uint32_t sub = 0;
-                for (int k = 0; k < 8; ++k) sub = std::max(sub, h.shard[k].p);
-                gridShort = c->mpuCount > 0 && sub > c->run.mpb * (c->run.mpuBlocks / 8u);
-                c->last.lastSubMax = sub;
-            } else {
-                c->last.lastSubMax = 0;
-            }
-            c->last.lastQueued = Q;
-            c->last.lastV = V;
-            c->last.haveQueued = c->mpuCount > 0;
-            c->seenV = std::max(c->seenV, V);
-            c->seenT = std::max(c->seenT, T);
-            c->seenShardV = std::max(c->seenShardV, mv);
-            c->seenShardT = std::max(c->seenShardT, mt);
-            if (!gridShort && V <= c->vcap && T <= c->tcap && mv <= c->vShardCap && mt <= c->tShardCap) break;
+        RunVerdict verdict;
+        for (int attempt = 0;; ++attempt) {
+            verdict = judge_run(h, c->run, c->mpuCount, caps_of(c));
+            c->last = verdict.last;
+            c->seen = caps_max(c->seen, verdict.used);
+            if (verdict.fits) break;
             if (attempt == 3) return PSGPU_RET_NOT_ENOUGH_MEM;  // still short after 3 regrowths
-            c->vcap = std::max(c->vcap, V + V / 8 + 1024);
-            c->tcap = std::max(c->tcap, T + T / 8 + 1024);
-            c->vShardCap = std::max(c->vShardCap, mv + mv / 4 + 256);
-            c->tShardCap = std::max(c->tShardCap, mt + mt / 4 + 256);
-            rc = ensure_buffers(c, c->mpuCount);
+            set_caps(c, grown(caps_of(c), verdict));
+            rc = ensure_buffers(c, bricks);
             if (rc != PSGPU_RET_SUCCESS) return rc;
-            rc = enqueue(c, c->runStream);
+            rc = enqueue(c, c->runStream, bricks);
             if (rc != PSGPU_RET_SUCCESS) return rc;
             PSGPU_CHECK(hipStreamSynchronize(c->runStream));
             reran = true;
@@ -1187,20 +769,21 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
                 if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess) c->lastMs[k] = ms;
             }
         }
-        const DevCounters& h = *c->hostCtr;
-        if (c->mpuCount && (h.error | h.surfaceErr)) {
+        if (verdict.protocol) {
             // an in-kernel wait gave up (an offsets-scan look-back, or k_surface's wait for the
             // scan): the run's offsets are not trusted.  Re-run it once as k_vertex + k_finish,
             // the chain whose kernel boundaries order the scan; a second error fails the call.
+            // Known gap (the open high finding): this re-run is checked for a second
+            // protocol error only, never judged against the grid and the capacities again.
             fprintf(stderr, "psgpu: device protocol error 0x%x (%s): re-running as separate launches\n",
-                    h.error | h.surfaceErr, c->run.front ? (c->run.surface ? "k_front, k_surface" : "k_front")
-                                                         : (c->run.surface ? "k_surface" : "k_vertex"));
-            rc = enqueue(c, c->runStream, true);
+                    verdict.protocol, c->run.front ? (c->run.surface ? "k_front, k_surface" : "k_front")
+                                                   : (c->run.surface ? "k_surface" : "k_vertex"));
+            rc = enqueue(c, c->runStream, bricks, true);
             if (rc != PSGPU_RET_SUCCESS) return rc;
             PSGPU_CHECK(hipStreamSynchronize(c->runStream));
             reran = true;
-            if (h.error | h.surfaceErr) {
-                fprintf(stderr, "psgpu: device protocol error 0x%x\n", h.error | h.surfaceErr);
+            if (protocol_error(h)) {
+                fprintf(stderr, "psgpu: device protocol error 0x%x\n", protocol_error(h));
                 return PSGPU_RET_DEVICE_ERROR;
             }
         }
@@ -1208,24 +791,10 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
             c->debug &= ~(1 << 21);
             return PSGPU_RET_DEVICE_ERROR;
         }
-        const ShardSums sum(h);
-        PsMeshInfo& I = c->info;
-        memset(&I, 0, sizeof(I));
-        I.ctMPUs = c->mpuCount;
-        I.ctPassedPrecheck = c->mpuCount ? sum.p + sum.b : 0;
-        I.ctSurfaceMPUs = c->mpuCount ? sum.s : 0;
-        I.ctVertices = c->mpuCount ? sum.v : 0;
-        I.ctTriangles = c->mpuCount ? sum.t : 0;
-        I.firstOverflowMPU = (c->mpuCount && h.firstOverflow != 0x7fffffff) ? h.firstOverflow : -1;
-        I.ctFieldMPUs = c->mpuCount ? sum.p : 0;
-        I.ctLaneEvals = 8ull * c->mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
-        I.launchFlags = c->mpuCount == 0 ? 0u
-                        : (c->run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (c->run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
-                              (c->run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u) |
-                              (c->run.sieve ? PSGPU_LAUNCH_SIEVE : 0u);
+        c->info = mesh_info(h, c->run, c->mpuCount, reran);
         c->haveResult = true;
         c->finishedSeq = c->runSeq;
-        if (c->countThreads) thread_results_add(c->serial, I.ctMPUs, I.ctSurfaceMPUs);
+        if (c->countThreads) thread_results_add(c->serial, c->info.ctMPUs, c->info.ctSurfaceMPUs);
     }
     if (!c->haveResult) return PSGPU_RET_PARAM_ERROR;
     if (info) *info = c->info;
@@ -1233,7 +802,7 @@ int psgpu_finish(psgpu_ctx* c, PsMeshInfo* info) {
 }
 
 int psgpu_download_stamps(psgpu_ctx* c, uint64_t* out, uint32_t* capOut) {
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     if (capOut) *capOut = c->stamps ? c->stampCap : 0u;
     if (!c->stamps || !out) return c->stamps ? PSGPU_RET_SUCCESS : PSGPU_RET_PARAM_ERROR;
@@ -1243,15 +812,13 @@ int psgpu_download_stamps(psgpu_ctx* c, uint64_t* out, uint32_t* capOut) {
 
 int psgpu_vertex_queue(psgpu_ctx* c, uint32_t* counts, uint32_t* recs, uint32_t capacity) {
     if (!c || !counts) return PSGPU_RET_PARAM_ERROR;
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     for (int k = 0; k < kShards; ++k) counts[k] = c->mpuCount ? c->hostCtr->shard[k].v : 0u;
     const ShardSums sum(*c->hostCtr);
     if (c->mpuCount && sum.maxV > c->vShardCap) return PSGPU_RET_DEVICE_ERROR;  // finish re-runs until they fit
     if (!recs) return PSGPU_RET_SUCCESS;
     if (c->mpuCount && sum.v > capacity) return PSGPU_RET_PARAM_ERROR;
-    rc = set_device(c);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
     std::vector<VertexKey> shard;
     for (int k = 0; k < kShards; ++k) {
         if (counts[k] == 0) continue;
@@ -1268,12 +835,10 @@ int psgpu_vertex_queue(psgpu_ctx* c, uint32_t* counts, uint32_t* recs, uint32_t 
 
 int psgpu_mpu_masks(psgpu_ctx* c, uint8_t* queued, uint64_t* masks, uint32_t capacity) {
     if (!c || !queued || !masks) return PSGPU_RET_PARAM_ERROR;
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     if (c->mpuCount > capacity) return PSGPU_RET_PARAM_ERROR;
     if (c->mpuCount == 0) return PSGPU_RET_SUCCESS;
-    rc = set_device(c);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
     const size_t n = c->mpuCount;
     PSGPU_CHECK(hipMemcpy(queued, c->passed, n, hipMemcpyDeviceToHost));
     PSGPU_CHECK(hipMemcpy(masks, c->mpuMasks, 4 * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -1287,7 +852,7 @@ int psgpu_mpu_masks(psgpu_ctx* c, uint8_t* queued, uint64_t* masks, uint32_t cap
 
 int psgpu_live_bricks(psgpu_ctx* c, uint32_t* bricks, uint32_t capacity, uint32_t* count) {
     if (!c || !count) return PSGPU_RET_PARAM_ERROR;
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     *count = 0;
     if (c->mpuCount == 0 || !c->run.sieve) return PSGPU_RET_SUCCESS;
@@ -1295,8 +860,6 @@ int psgpu_live_bricks(psgpu_ctx* c, uint32_t* bricks, uint32_t capacity, uint32_
     *count = n;
     if (!bricks || n == 0) return PSGPU_RET_SUCCESS;
     if (n > capacity || n > c->liveList.cap) return PSGPU_RET_PARAM_ERROR;
-    rc = set_device(c);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
     std::vector<uint64_t> raw(n);
     PSGPU_CHECK(hipMemcpy(raw.data(), c->liveList, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < n; ++k) {
@@ -1366,7 +929,7 @@ int psgpu_last_kernel_times(psgpu_ctx* c, float* ms, int maxKernels, const char*
 
 int psgpu_mesh_device(psgpu_ctx* c, PsMeshDevice* out) {
     if (!c || !out) return PSGPU_RET_PARAM_ERROR;
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     out->pos = c->pos;
     out->nrm = c->nrm;
@@ -1378,7 +941,7 @@ int psgpu_mesh_device(psgpu_ctx* c, PsMeshDevice* out) {
 
 int psgpu_download_mesh(psgpu_ctx* c, float* pos, float* nrm, float* col, uint32_t* tris, uint64_t* mpuOffsets) {
     PsMeshInfo I;
-    int rc = psgpu_finish(c, &I);
+    int rc = finished_run(c, &I);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     const size_t V = I.ctVertices, T = I.ctTriangles, N = I.ctMPUs;
     if (pos && V) PSGPU_CHECK(hipMemcpy(pos, c->pos, V * 12, hipMemcpyDeviceToHost));
@@ -1407,7 +970,7 @@ int survivors(psgpu_ctx* c, std::vector<uint32_t>& ids) {
 
 int psgpu_download_stats(psgpu_ctx* c, PsMpuStats* stats) {
     PsMeshInfo I;
-    int rc = psgpu_finish(c, &I);
+    int rc = finished_run(c, &I);
     if (rc != PSGPU_RET_SUCCESS || !stats) return rc == PSGPU_RET_SUCCESS ? PSGPU_RET_PARAM_ERROR : rc;
     std::vector<uint32_t> ids;
     rc = survivors(c, ids);
@@ -1433,7 +996,7 @@ int psgpu_download_stats(psgpu_ctx* c, PsMpuStats* stats) {
 // between two host readings; of 8 tries the tightest bracket gives the offset, which is then
 // good to half its width (a few microseconds; MPU ticks are tens of microseconds apart).
 int psgpu_download_process_stats(psgpu_ctx* c, PsMpuProcessStats* out) {
-    int rc = psgpu_finish(c, nullptr);
+    int rc = finished_run(c);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     if (!out || !c->runTicks) return PSGPU_RET_PARAM_ERROR;
     const uint32_t n = c->mpuCount;
@@ -1490,7 +1053,7 @@ int psgpu_download_process_stats(psgpu_ctx* c, PsMpuProcessStats* out) {
 // samples, value and 3 normal samples).  Balances MPU ranges across devices.
 int psgpu_mpu_costs(psgpu_ctx* c, uint32_t* costs) {
     PsMeshInfo I;
-    int rc = psgpu_finish(c, &I);
+    int rc = finished_run(c, &I);
     if (rc != PSGPU_RET_SUCCESS) return rc;
     if (!costs) return PSGPU_RET_PARAM_ERROR;
     const uint32_t n = c->mpuCount;
@@ -1504,340 +1067,8 @@ int psgpu_mpu_costs(psgpu_ctx* c, uint32_t* costs) {
     return PSGPU_RET_SUCCESS;
 }
 
-// Contiguous ranges of near-equal cost: bounds[k] = begin + the first index whose cost
-// prefix reaches k/parts of the total (bounds[0] = begin, bounds[parts] = begin + n).
 int psgpu_split_costs(const uint32_t* costs, uint32_t n, uint32_t parts, uint32_t begin, uint32_t* bounds) {
-    if (!bounds || parts == 0 || (n && !costs)) return PSGPU_RET_PARAM_ERROR;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) total += costs[i];
-    bounds[0] = begin;
-    uint64_t acc = 0;
-    uint32_t i = 0;
-    for (uint32_t k = 1; k < parts; ++k) {
-        const uint64_t target = (total * k + parts / 2) / parts;
-        while (i < n && acc + costs[i] / 2 < target) acc += costs[i++];
-        bounds[k] = begin + i;
-    }
-    bounds[parts] = begin + n;
-    return PSGPU_RET_SUCCESS;
-}
-
-}  // extern "C"
-
-namespace psgpu {
-// The blocking export (Polygonize :360-371 into PolyMPUs, and the MPUSTATS of :372-376): one
-// batch of async copies of the compact mesh, offsets, S1 flags and (for stats) counts into the
-// context's pinned staging buffer (export_stage), one wait, then the host scatter
-// (export_scatter).  Pageable destinations would cost a staged copy and a wait each (7 of
-// them for a mesh plus statistics).  A group stages every part before it scatters the first,
-// so the later parts' copies overlap the earlier parts' scatter.  Call after psgpu_finish.
-int export_stage(psgpu_ctx* c, bool mesh, bool stats, ExportStage* st, hipEvent_t after) {
-    const PsMeshInfo& I = c->info;
-    ExportStage& S = *st;
-    S.mesh = mesh;
-    S.stats = stats;
-    S.V = mesh ? I.ctVertices : 0;
-    S.T = mesh ? I.ctTriangles : 0;
-    S.N = c->mpuCount;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t N = S.N, V = S.V, T = S.T;
-    // The per-piece flags sit at the front of the staging, at an offset no call moves: those
-    // words only ever hold flags (an older call's epoch, or 0), never mesh or offset words, so
-    // no stale word can equal this call's epoch (r04 kept them behind the mesh, where a call
-    // with a smaller mesh found the previous call's packed triangles and offsets -- ADVICE r04)
-    const size_t flagBytes = 4 * (size_t)kExportPieces * kExportPackBlocks * kExportFlagStride;
-    S.oFlags = 0;
-    S.oOffs = up(flagBytes);
-    S.oPass = up(S.oOffs + (N + 1) * 8);
-    S.oCnt = up(S.oPass + N);
-    S.oMesh = up(S.oCnt + (stats ? N * 8 : 0));
-    // the packed mesh: pack_words per piece; bounded by 4 extra words per piece
-    S.meshBytes = mesh ? 4 * (pack_words(V, T) + 4 * kExportPieces) : 0;
-    const size_t total = up(S.oMesh + S.meshBytes);
-    if (total > c->hostStage.cap) {
-        // coherent: the export kernels write it directly over PCIe
-        PSGPU_CHECK(c->hostStage.reserve(total + total / 4, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(c->hostStage, 0, c->hostStage.cap);  // no stale flag can equal an epoch
-    }
-    if (++c->exportEpoch == 0) {  // wrapped: clear every old flag
-        memset(c->hostStage, 0, c->hostStage.cap);
-        c->exportEpoch = 1;
-    }
-    S.epoch = c->exportEpoch;
-    unsigned char* h = c->hostStage;
-    if (c->debug & (1 << 23)) {  // test hook: every word past the flags reads as this call's epoch
-        // (the stream is idle: the previous export's scatter synchronised with it)
-        uint32_t* w = reinterpret_cast<uint32_t*>(h + flagBytes);
-        for (size_t i = 0, n = (c->hostStage.cap - flagBytes) / 4; i < n; ++i) w[i] = S.epoch;
-    }
-    hipStream_t s = c->stream;
-    for (hipEvent_t& e : c->exportEv)
-        if (!e) PSGPU_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    unsigned char* hd = nullptr;  // the staging as the device addresses it
-    PSGPU_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd), h, 0));
-    if (N) {
-        MetaSrc ms{mesh ? c->offs : nullptr, c->passed, stats ? c->counts : nullptr, (uint32_t)N,
-                   S.oOffs, S.oPass, S.oCnt};
-        PSGPU_CHECK(launch_export_meta(ms, hd, s));
-    }
-    PSGPU_CHECK(hipEventRecord(c->exportEv[0], s));
-    // the mesh packed piece by piece (MPU ranges of about 1 MB of mesh, at most 16: C3 0.535 vs
-    // 0.570 ms with 2 MB) into one contiguous region by one kernel writing it over PCIe; the
-    // host scatter of one piece overlaps the transfer of the next
-    // 256 blocks: one wave per SIMD keeps the link busy; 1,024 or 2,048 were 1.8-4.5x slower,
-    // every block's per-piece release (an L2 write-back) adding up (r04)
-    S.packBlocks = kExportPackBlocks;
-    S.pieces = (int)std::min<size_t>({(size_t)kExportPieces, std::max<size_t>(N, 1),
-                                      1 + 4 * pack_words(V, T) / kExportPieceBytes});
-    if (after) PSGPU_CHECK(hipStreamWaitEvent(s, after, 0));
-    if (S.meshBytes && N) {
-        PackSrc src{c->offs, c->pos, c->nrm, c->col, c->tris, (uint32_t)N, (uint32_t)S.pieces,
-                    reinterpret_cast<uint32_t*>(hd + S.oFlags), S.epoch, S.packBlocks,
-                    // test hook: the last block waits ~40 us before each piece's share
-                    (c->debug & (1 << 24)) ? S.packBlocks - 1u : 0xffffffffu, 4000u};
-        PSGPU_CHECK(launch_export_pack(src, reinterpret_cast<uint32_t*>(hd + S.oMesh), s));
-    }
-    PSGPU_CHECK(hipEventRecord(c->exportEv[1], s));
-    return PSGPU_RET_SUCCESS;
-}
-
-int ScatterJob::prepare(psgpu_ctx* ctx, const ExportStage& st, PsMPU* out) {
-    c = ctx;
-    S = &st;
-    mpus = out;
-    PSGPU_CHECK(hipEventSynchronize(c->exportEv[0]));  // offsets, S1 flags, counts
-    const unsigned char* h = c->hostStage;
-    off = reinterpret_cast<const uint64_t*>(h + st.oOffs);
-    passed = h + st.oPass;
-    mesh = h + st.oMesh;
-    flags = reinterpret_cast<const uint32_t*>(h + st.oFlags);
-    side = c->cs * (float)PSGPU_CELLS_PER_MPU;
-    active = out && st.mesh && !(c->debug & (1 << 22));  // bit 22: the transfers without the scatter
-    if (!active) return PSGPU_RET_SUCCESS;
-    // the pieces' MPU ranges and their places in the packed mesh (as k_export_pack laid them out)
-    const size_t N = st.N;
-    size_t base = 0;
-    for (int k = 0; k <= st.pieces; ++k) pm[k] = (uint32_t)((uint64_t)N * (uint64_t)k / (uint64_t)st.pieces);
-    for (int k = 0; k < st.pieces; ++k) {
-        pv0[k] = (uint32_t)off[pm[k]];
-        pt0[k] = (uint32_t)(off[pm[k]] >> 32);
-        pnv[k] = (uint32_t)off[pm[k + 1]] - pv0[k];
-        pbase[k] = base;
-        base += 4 * pack_words(pnv[k], (uint32_t)(off[pm[k + 1]] >> 32) - pt0[k]);
-    }
-    return PSGPU_RET_SUCCESS;
-}
-
-// piece k is in when every block of k_export_pack has raised its flag for it; the kernel's
-// event ends the wait should it fail.  One thread at a time reads the flags (they sit in
-// memory the device writes over PCIe: sixteen threads polling them slowed the device's
-// writes in some calls) and publishes the count of pieces in; the others watch that count.
-bool ScatterJob::wait_piece(int k) {
-    for (uint32_t spin = 1;; ++spin) {
-        const int r = ready.load(std::memory_order_acquire);
-        if (r > k) return true;
-        if (r < 0) return false;  // the kernel failed
-        bool idle = false;
-        if (polling.compare_exchange_strong(idle, true, std::memory_order_acq_rel)) {
-            int n = ready.load(std::memory_order_acquire);
-            while (n >= 0 && n < S->pieces) {  // advance over every piece already in
-                const uint32_t* f = flags + (size_t)n * S->packBlocks * kExportFlagStride;
-                // from the first flag not yet seen up: every read of a flag still down is a read
-                // of a line the device is about to write (one flag a line, kExportFlagStride)
-                uint32_t b = pollBlock;
-                while (b < S->packBlocks && __atomic_load_n(f + (size_t)b * kExportFlagStride, __ATOMIC_ACQUIRE) == S->epoch) ++b;
-                pollBlock = b;
-                if (b < S->packBlocks) {
-                    if ((spin & 63) == 0) {
-                        const hipError_t e = hipEventQuery(c->exportEv[1]);
-                        if (e != hipErrorNotReady) {  // done (every flag must be up) or failed
-                            while (b < S->packBlocks && __atomic_load_n(f + (size_t)b * kExportFlagStride, __ATOMIC_ACQUIRE) == S->epoch) ++b;
-                            if (e != hipSuccess || b < S->packBlocks) n = -1;
-                            else ++n;
-                            pollBlock = 0;
-                            ready.store(n, std::memory_order_release);
-                            continue;
-                        }
-                    }
-                    break;
-                }
-                if (trace) tPiece[n] = now_ns();
-                pollBlock = 0;
-                ready.store(++n, std::memory_order_release);
-            }
-            polling.store(false, std::memory_order_release);
-            for (int i = 0; i < 256; ++i) __builtin_ia32_pause();  // ~1-2 us between reads of the flags
-        }
-        std::this_thread::yield();
-    }
-}
-
-// MPUs [lb, le) into PolyMPUs (Polygonize :360-371); `have` = the pieces this thread has seen in
-bool ScatterJob::range(uint32_t lb, uint32_t le, int* have) {
-    int k = 0;
-    while (k + 1 < S->pieces && lb >= pm[k + 1]) ++k;
-    for (uint32_t l = lb; l < le; ++l) {
-        while (k + 1 < S->pieces && l >= pm[k + 1]) ++k;
-        const uint32_t v0 = (uint32_t)off[l], nv = (uint32_t)off[l + 1] - v0;
-        const uint32_t t0 = (uint32_t)(off[l] >> 32), nt = (uint32_t)(off[l + 1] >> 32) - t0;
-        const unsigned char* P = mesh + pbase[k];
-        const float* pos = reinterpret_cast<const float*>(P) + 3 * (v0 - pv0[k]);
-        const float* nrm = reinterpret_cast<const float*>(P + pnv[k] * 12) + 3 * (v0 - pv0[k]);
-        const float* col = reinterpret_cast<const float*>(P + pnv[k] * 24) + 3 * (v0 - pv0[k]);
-        const uint16_t* tri = reinterpret_cast<const uint16_t*>(P + pnv[k] * 36) + 3 * (t0 - pt0[k]);
-        while (*have <= k) {  // this MPU's piece written (the pieces come in order)
-            if (!wait_piece(*have)) return false;
-            ++*have;
-        }
-        const uint32_t m = c->mpuBegin + l;
-        const uint32_t kk = m % c->dims[2], j = (m / c->dims[2]) % c->dims[1], i = m / (c->dims[2] * c->dims[1]);
-        PsMPU& M = mpus[l];
-        M.bboxLo.x = c->primsHost.bboxLo.x + (float)i * side;
-        M.bboxLo.y = c->primsHost.bboxLo.y + (float)j * side;
-        M.bboxLo.z = c->primsHost.bboxLo.z + (float)kk * side;
-        M.ctFieldEvals = passed[l] ? 128 : 0;
-        M.ctVertices = (uint16_t)nv;
-        M.ctTriangles = (uint16_t)nt;
-        memcpy(M.vPos, pos, (size_t)nv * 12);
-        memcpy(M.vNorm, nrm, (size_t)nv * 12);
-        memcpy(M.vColor, col, (size_t)nv * 12);
-        memcpy(M.triangles, tri, (size_t)nt * 6);
-    }
-    return true;
-}
-
-// thread k of nth: chunks of 128 MPUs dealt round robin (the surface lies in a few slabs of
-// the range), in ascending order, so the pieces are waited for in the order they come
-void ScatterJob::task(unsigned k, unsigned nth) {
-    if (!active) return;
-    if (trace) {
-        int64_t z = 0;
-        (void)tFirstTask.compare_exchange_strong(z, now_ns());
-    }
-    int have = 0;
-    const uint32_t N = (uint32_t)S->N;
-    for (uint32_t b = k * 128u; b < N; b += nth * 128u)
-        if (!range(b, std::min<uint32_t>(N, b + 128u), &have)) {
-            failed = true;
-            return;
-        }
-}
-
-int ScatterJob::finish(PsMpuStats* stats) {
-    if (failed) return PSGPU_RET_DEVICE_ERROR;
-    PSGPU_CHECK(hipStreamSynchronize(c->stream));  // the packing kernel done
-    if (stats && S->stats) {
-        const uint64_t* cnt = reinterpret_cast<const uint64_t*>(c->hostStage + S->oCnt);
-        memset(stats, 0, sizeof(PsMpuStats) * S->N);
-        for (uint32_t l = 0; l < S->N; ++l) {
-            PsMpuStats& st = stats[l];
-            if (passed[l]) {
-                st.passedPrecheck = 1;
-                st.ctFieldEvals = 128;
-            }
-            st.ctVertices = (uint32_t)(cnt[l] & 0xffffffffu);
-            st.ctTriangles = (uint32_t)(cnt[l] >> 32);
-        }
-    }
-    return PSGPU_RET_SUCCESS;
-}
-
-// The scatter is bound by the write-allocates of the sparse PolyMPUs layout (21.5 KB per MPU):
-// several host threads, as the reference's TBB bodies fill it -- about one per 256 KB of mesh,
-// at most 16 (C3 0.535 vs 0.586 ms with 8), kept in c's pool.  Runs jobs[0..n) in one pass: every thread takes its chunks of
-// each job in turn.
-int scatter_jobs(psgpu_ctx* c, ScatterJob* jobs, size_t n) {
-    size_t bytes = 0;
-    for (size_t j = 0; j < n; ++j) bytes += jobs[j].active ? jobs[j].S->meshBytes : 0;
-    const unsigned nth = (unsigned)std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()),
-                                                    1 + bytes / (256 << 10)});
-    std::function<void(unsigned)> task = [&](unsigned k) {
-        for (size_t j = 0; j < n; ++j) jobs[j].task(k, nth);
-    };
-    // nth workers on the caller's NUMA node; the caller only waits
-    if (nth > 1 && (!c->scatterPool || c->scatterPool->workers() < nth)) {
-        c->scatterPool.reset();
-        try {
-            cpu_set_t node;
-            const bool haveNode = ScatterPool::caller_node_cpus(&node);
-            c->scatterPool.reset(new ScatterPool(nth, haveNode ? &node : nullptr));
-        } catch (...) {  // no threads to be had: this caller scatters alone
-            c->scatterPool.reset();
-        }
-    }
-    if (nth > 1 && c->scatterPool) c->scatterPool->run(nth, task, false);
-    else
-        for (unsigned k = 0; k < nth; ++k) task(k);
-    return PSGPU_RET_SUCCESS;
-}
-
-// PSGPU_EXPORT_TRACE=1: every blocking export prints its phases (ms from the call's start) to
-// stderr -- kernels done, packing enqueued, metadata in, first scatter task, each piece in,
-// scatter done, end (tools/blocking_seq.py collects them)
-bool export_trace_on() {
-    static const bool on = [] {
-        const char* e = getenv("PSGPU_EXPORT_TRACE");
-        return e && *e && *e != '0';
-    }();
-    return on;
-}
-
-int export_scatter(psgpu_ctx* c, const ExportStage& S, PsMPU* mpus, PsMpuStats* stats, const int64_t* tr) {
-    ScatterJob job;
-    job.trace = tr != nullptr;
-    int rc = job.prepare(c, S, mpus);
-    const int64_t tPrep = tr ? now_ns() : 0;
-    if (rc == PSGPU_RET_SUCCESS) rc = scatter_jobs(c, &job, 1);
-    const int64_t tScat = tr ? now_ns() : 0;
-    if (rc == PSGPU_RET_SUCCESS) rc = job.finish(stats);
-    if (tr) {
-        const int64_t t0 = tr[0], tEnd = now_ns();
-        auto ms = [t0](int64_t t) { return t ? (double)(t - t0) * 1e-6 : -1.0; };
-        fprintf(stderr, "psgpu export: mpus %zu V %zu pieces %d | kernels %.3f packing %.3f meta %.3f first_task %.3f pieces",
-                S.N, S.V, S.pieces, ms(tr[1]), ms(tr[2]), ms(tPrep), ms(job.tFirstTask.load()));
-        for (int k = 0; k < S.pieces; ++k) fprintf(stderr, " %.3f", ms(job.tPiece[k]));
-        fprintf(stderr, " | scatter %.3f end %.3f\n", ms(tScat), ms(tEnd));
-    }
-    return rc;
-}
-}  // namespace psgpu
-
-namespace {
-int export_blocking(psgpu_ctx* c, PsMPU* mpus, uint32_t capacity, uint32_t* outCt, PsMpuStats* stats,
-                    int64_t tCall = 0) {
-    int64_t tr[3] = {tCall ? tCall : now_ns(), 0, 0};
-    const bool trace = export_trace_on();
-    PsMeshInfo I;
-    int rc = psgpu_finish(c, &I);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    tr[1] = now_ns();
-    if (outCt) *outCt = c->mpuCount;
-    if (mpus) {
-        if (c->mpuCount > capacity) return PSGPU_RET_MPU_OVERFLOW;
-        if (I.firstOverflowMPU >= 0) return PSGPU_RET_MPU_VT_OVERFLOW;
-    }
-    if (!mpus && !stats) return PSGPU_RET_PARAM_ERROR;
-    ExportStage st;
-    rc = export_stage(c, mpus != nullptr, stats != nullptr, &st);
-    if (rc != PSGPU_RET_SUCCESS) return rc;
-    tr[2] = now_ns();
-    return export_scatter(c, st, mpus, stats, trace ? tr : nullptr);
-}
-}  // namespace
-
-extern "C" {
-
-int psgpu_export_polympus(psgpu_ctx* c, PsMPU* mpus, uint32_t capacity, uint32_t* outCt) {
-    if (!mpus) {  // the count (and overflow) check alone
-        PsMeshInfo I;
-        int rc = psgpu_finish(c, &I);
-        if (rc != PSGPU_RET_SUCCESS) return rc;
-        if (outCt) *outCt = c->mpuCount;
-        if (c->mpuCount > capacity) return PSGPU_RET_MPU_OVERFLOW;
-        if (I.firstOverflowMPU >= 0) return PSGPU_RET_MPU_VT_OVERFLOW;
-        return PSGPU_RET_PARAM_ERROR;
-    }
-    return export_blocking(c, mpus, capacity, outCt, nullptr);
+    return split_costs(costs, n, parts, begin, bounds);
 }
 
 int psgpu_polygonize_mpus(psgpu_ctx* c, float cellsize, const PsSoaBlobPrims* prims, const PsSoaPrimMatrices* mats,
@@ -1885,7 +1116,8 @@ int psgpu_field_values(psgpu_ctx* c, const float* xyz, uint32_t n, int mode, flo
     PSGPU_CHECK(bcol.reserve((size_t)n * 3, Growth::Exact));
     float *dx = bx, *dout = bout, *dcol = bcol;
     PSGPU_CHECK(hipMemcpy(dx, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
-    Params p = make_params(c, plan_run(c, false));
+    const BrickLayout bricks = run_bricks(c);
+    Params p = make_params(c, bricks, plan_run(c, bricks, false));
     hipError_t e;
     if (c->jit.kernels) {
         void* args[] = {&p, &dx, &dout, &dcol, &n, &mode};

@@ -1,6 +1,6 @@
 // psgpu_internal.h — the device context shared by the library's host sources
-// (psgpu_host.cpp: one context, psgpu_group.cpp: contexts over several devices and the
-// multi-process count exchange).  Not part of the C-ABI.
+// (psgpu_host.cpp: one context, psgpu_export.cpp: its blocking export, psgpu_group.cpp: contexts
+// over several devices and the multi-process count exchange).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,7 +21,7 @@
 
 namespace psgpu {
 constexpr int kNumKernels = 4;
-constexpr int kExportPieces = 16;  // at most, in the blocking export (psgpu_host.cpp export_stage)
+constexpr int kExportPieces = 16;  // at most, in the blocking export (psgpu_export.cpp export_stage)
 constexpr size_t kExportPieceBytes = 1u << 20;  // its target piece size
 
 // The device weld of a finished run (psgpu_weld.hip): its own buffers, allocated on the first
@@ -186,7 +186,7 @@ struct psgpu_ctx {
     PsMeshInfo info{};
     // high-water marks of finished runs: the next run's buffers are sized from them
     // (an animation whose mesh grows frame to frame does not pay a synchronous re-run)
-    uint32_t seenV = 0, seenT = 0, seenShardV = 0, seenShardT = 0;
+    psgpu::Caps seen{};
     // psgpu_weld: runSeq counts whatever supersedes a result (set_model, polygonize, a
     // capacity restart), finishedSeq is its value when psgpu_finish last collected a run
     uint64_t runSeq = 0, finishedSeq = ~0ull;
@@ -198,6 +198,10 @@ namespace psgpu {
 int hip_fail(hipError_t e, const char* what);
 // Make the context's device current on the calling thread.
 int set_device(psgpu_ctx* c);
+// The one way to a collected run, for every entry point that reads a finished run's buffers:
+// psgpu_finish (which makes the device current only while a run is pending), then set_device --
+// the calling thread may have used another device since.  PARAM_ERROR for a null context.
+int finished_run(psgpu_ctx* c, PsMeshInfo* info = nullptr);
 // Free a weld's buffers and events (psgpu_weld.hip), a context's or a group's; its device is current.
 void weld_state_free(WeldState& W);
 // The context's run is finished, superseded by nothing newer, and whole: it can be welded;
@@ -252,7 +256,7 @@ int filter_device(const WeldState& W, PsFilterDevice* out);
 int filter_download(const WeldState& W, float* pos, float* nrm, float* col, uint32_t* tris, uint32_t* vertexMap,
                     uint32_t* shellMap, PsShell* shells, uint32_t shellCapacity);
 int filter_times(const WeldState& W, float* ms, int maxPhases, const char** names);
-// The blocking export of a finished run in two steps (psgpu_host.cpp): enqueue the copies of
+// The blocking export of a finished run in two steps (psgpu_export.cpp): enqueue the copies of
 // the compact mesh (mesh), the S1 flags and (stats) the per-MPU counts into the context's
 // pinned staging buffer, then wait and scatter into PolyMPUs / PsMpuStats.
 struct ExportStage {
@@ -305,6 +309,9 @@ struct ScatterJob {
     int finish(PsMpuStats* stats);
 };
 int scatter_jobs(psgpu_ctx* c, ScatterJob* jobs, size_t n);
+// One context's blocking export, run collected first (psgpu_export_polympus, psgpu_polygonize_mpus).
+// tCall: when the caller's call began, for PSGPU_EXPORT_TRACE (0: now).
+int export_blocking(psgpu_ctx* c, PsMPU* mpus, uint32_t capacity, uint32_t* outCt, PsMpuStats* stats, int64_t tCall = 0);
 }  // namespace psgpu
 
 #define PSGPU_CHECK(expr)                                           \

@@ -7,13 +7,20 @@
 // its hipGraph replay on the plan's bytes and reports it as PsMeshInfo.launchFlags.  LDS sizes
 // are not part of it (they need the device header).
 //
-// Host only, and not embedded for hiprtc.  A plain C++ program (tests/cpp/plan_check.cpp)
-// defines PSGPU_MODEL_NO_HIP first and needs no ROCm headers.
+// The other end of a run is decided here too: judge_run() turns a finished run's counters, its
+// plan and the context's capacities into "fits", "grow to these capacities and re-run" or
+// "protocol error", and mesh_info() into the PsMeshInfo the caller sees (psgpu_finish).
+//
+// Host only, and not embedded for hiprtc.  A plain C++ program (tests/cpp/plan_check.cpp,
+// run_verdict_check.cpp) defines PSGPU_MODEL_NO_HIP first and needs no ROCm headers.
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
+#include <numeric>
 
+#include "../../include/parsip_gpu.h"
 #include "psgpu_model.h"
 
 namespace psgpu {
@@ -80,6 +87,39 @@ static_assert(sizeof(LaunchPlan) == 4 + 12 * sizeof(uint32_t), "no padding: plan
 // k_front sub-queue capacity for a k_precheck grid of `blocks` blocks of `mpb` bricks: every
 // 8th block's bricks x 8 MPUs
 inline uint32_t front_sub_cap(uint32_t blocks, uint32_t mpb) { return 8u * mpb * ((blocks + 7u) / 8u); }
+// ... for both k_precheck grids (2 and 4 bricks per block)
+inline uint32_t front_cap(uint64_t bricks) {
+    const uint32_t b = (uint32_t)bricks;
+    return std::max(front_sub_cap((b + 1u) / 2u, 2u), front_sub_cap((b + 3u) / 4u, 4u));
+}
+
+// k_precheck covers the MPU range with 2x2x2 bricks of MPUs (one per wavefront: a
+// compact box for its culling test), whole brick rows along x: the first brick row and the
+// bricks along each axis (Params::brickI0, brickDims).
+struct BrickLayout {
+    uint32_t i0 = 0, dims[3] = {0, 0, 0};
+};
+inline BrickLayout brick_layout(const uint32_t dims[3], uint32_t mpuBegin, uint32_t mpuCount) {
+    const uint32_t nyz = dims[1] * dims[2];
+    const uint32_t first = nyz ? mpuBegin / nyz : 0;
+    const uint32_t last = (nyz && mpuCount) ? (mpuBegin + mpuCount - 1) / nyz : first;
+    BrickLayout b;
+    b.i0 = first / 2;
+    b.dims[0] = mpuCount ? last / 2 - first / 2 + 1 : 0;
+    b.dims[1] = (dims[1] + 1) / 2;
+    b.dims[2] = (dims[2] + 1) / 2;
+    return b;
+}
+inline uint64_t brick_count(const BrickLayout& b) { return (uint64_t)b.dims[0] * b.dims[1] * b.dims[2]; }
+// The brick permutation of k_precheck: stride 1 keeps the lattice order; otherwise a
+// stride near n / golden ratio, coprime with n, so consecutive wave slots (one block, one
+// CU) take bricks far apart and the bricks crossed by the surface spread over the chip.
+inline uint32_t brick_stride(uint32_t n, bool spread) {
+    if (!spread || n < 3) return 1u;
+    for (uint32_t s = (uint32_t)(n * 0.6180339887) | 1u; s > 1; --s)
+        if (std::gcd(s, n) == 1u) return s;
+    return 1u;
+}
 
 inline LaunchPlan plan_launch(const PlanInput& in) {
     const LaunchOptions& o = in.opt;
@@ -200,6 +240,99 @@ inline LaunchPlan plan_launch(const PlanInput& in) {
         pl.gridFinish = fitted(persistF, 4ull * pl.vpwFinish);
     }
     return pl;
+}
+
+// ---------------------------------------------------------------------------
+// The verdict on a finished run.
+
+// A finished run's counters over its shards: sums, and the largest shard's vertices and triangles.
+struct ShardSums {
+    uint32_t v = 0, t = 0, s = 0, p = 0, b = 0, maxV = 0, maxT = 0;
+    explicit ShardSums(const DevCounters& h) {
+        for (int k = 0; k < kShards; ++k) {
+            v += h.shard[k].v;
+            t += h.shard[k].t;
+            s += h.shard[k].s;
+            p += h.shard[k].p;
+            b += h.shard[k].b;
+            maxV = std::max(maxV, h.shard[k].v);
+            maxT = std::max(maxT, h.shard[k].t);
+        }
+    }
+};
+
+// What a run may write: the compact mesh's vertices and triangles, and each shard's vertex and
+// triangle records.  Also what a run did write (RunVerdict::used) and the most any run has.
+struct Caps {
+    uint32_t v, t, shardV, shardT;
+};
+inline bool within(const Caps& a, const Caps& cap) {
+    return a.v <= cap.v && a.t <= cap.t && a.shardV <= cap.shardV && a.shardT <= cap.shardT;
+}
+inline Caps caps_max(const Caps& a, const Caps& b) {
+    return {std::max(a.v, b.v), std::max(a.t, b.t), std::max(a.shardV, b.shardV), std::max(a.shardT, b.shardT)};
+}
+
+inline uint32_t protocol_error(const DevCounters& h) { return h.error | h.surfaceErr; }
+
+struct RunVerdict {
+    Caps used;           // what the run appended (the device counts past a full buffer, writing nothing)
+    LastRun last;        // what it leaves for sizing the next run
+    bool gridShort;      // S1 queued more than the run's S2 blocks take
+    bool fits;           // the grid and the four capacities held: the output is whole
+    uint32_t protocol;   // an in-kernel wait gave up (DevCounters::error | surfaceErr); 0 for an empty range
+};
+
+// `h`: the counters k_finish published, `run`: the plan the run was launched with.  An empty range
+// launches nothing: its grid is never short and it has no protocol error, but the counters (the
+// host zeroes them for such a run) are still held against the capacities.
+inline RunVerdict judge_run(const DevCounters& h, const LaunchPlan& run, uint32_t mpuCount, const Caps& caps) {
+    const ShardSums sum(h);
+    RunVerdict r{};
+    r.used = {sum.v, sum.t, sum.maxV, sum.maxT};
+    r.gridShort = mpuCount > 0 && sum.p > run.mpb * run.mpuBlocks;
+    if (run.front) {  // k_front: each sub-queue against its own rows of S2 blocks
+        uint32_t sub = 0;
+        for (int k = 0; k < 8; ++k) sub = std::max(sub, h.shard[k].p);
+        r.gridShort = mpuCount > 0 && sub > run.mpb * (run.mpuBlocks / 8u);
+        r.last.lastSubMax = sub;
+    }
+    r.last.lastQueued = sum.p;
+    r.last.lastV = sum.v;
+    r.last.haveQueued = mpuCount > 0;
+    r.fits = !r.gridShort && within(r.used, caps);
+    r.protocol = mpuCount ? protocol_error(h) : 0u;
+    return r;
+}
+
+// The capacities to re-run a run that did not fit with: what it used and a margin, never less than before.
+inline Caps grown(const Caps& caps, const RunVerdict& r) {
+    const Caps& u = r.used;
+    return caps_max(caps, {u.v + u.v / 8 + 1024, u.t + u.t / 8 + 1024, u.shardV + u.shardV / 4 + 256, u.shardT + u.shardT / 4 + 256});
+}
+// The capacities of the next run from the most any finished run used: + 1/4, never less than before.
+inline Caps grown_ahead(const Caps& caps, const Caps& seen) {
+    return caps_max(caps, {seen.v + seen.v / 4, seen.t + seen.t / 4, seen.shardV + seen.shardV / 4, seen.shardT + seen.shardT / 4});
+}
+
+// What psgpu_finish reports of a collected run.  reran: finish launched it more than once.
+inline PsMeshInfo mesh_info(const DevCounters& h, const LaunchPlan& run, uint32_t mpuCount, bool reran) {
+    const ShardSums sum(h);
+    PsMeshInfo I;
+    memset(&I, 0, sizeof(I));
+    I.ctMPUs = mpuCount;
+    I.ctPassedPrecheck = mpuCount ? sum.p + sum.b : 0;
+    I.ctSurfaceMPUs = mpuCount ? sum.s : 0;
+    I.ctVertices = mpuCount ? sum.v : 0;
+    I.ctTriangles = mpuCount ? sum.t : 0;
+    I.firstOverflowMPU = (mpuCount && h.firstOverflow != 0x7fffffff) ? h.firstOverflow : -1;
+    I.ctFieldMPUs = mpuCount ? sum.p : 0;
+    I.ctLaneEvals = 8ull * mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
+    I.launchFlags = mpuCount == 0 ? 0u
+                    : (run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
+                          (run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u) |
+                          (run.sieve ? PSGPU_LAUNCH_SIEVE : 0u);
+    return I;
 }
 
 }  // namespace psgpu

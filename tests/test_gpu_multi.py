@@ -356,6 +356,40 @@ def test_rccl_two_ranks_one_rerun(tmp_path):
         assert p.returncode == 0, e[-2000:]
 
 
+def test_downloads_after_the_thread_used_another_device():
+    """Every download of a collected run makes its context's device current first (finished_run,
+    psgpu_host.cpp): a context on device 1 runs and finishes, the same thread then creates and
+    uses a context on device 0, and the first context's mesh, statistics, costs and stamps still
+    come back as they did before the device changed (needs 2 GPUs)."""
+    if gpu.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    model, cs, _ = synth.make_config("C1")
+    first, other = gpu.Polygonizer(1), None
+    try:
+        first.set_option(gpu.OPT_STAMPS, 256)
+        first.set_model(model)
+        info = first.run(cs)
+        assert info.ctVertices > 0
+        before = (first.download(), first.stats(), first.mpu_costs(), first.stamps())
+        other = gpu.Polygonizer(0)  # the calling thread's current device is now 0
+        other.set_model(model)
+        assert other.run(cs).ctVertices == info.ctVertices
+        after = (first.download(), first.stats(), first.mpu_costs(), first.stamps())
+    finally:
+        first.close()
+        if other is not None:
+            other.close()
+    for name in ("pos", "nrm", "col"):
+        assert_bits_equal(getattr(after[0], name), getattr(before[0], name), name)
+    for name in ("tris", "vertex_offsets", "triangle_offsets"):
+        np.testing.assert_array_equal(getattr(after[0], name), getattr(before[0], name), err_msg=name)
+    assert after[1].tobytes() == before[1].tobytes(), "stats"
+    np.testing.assert_array_equal(after[2], before[2], err_msg="mpu_costs")
+    assert after[3].keys() == before[3].keys() and len(before[3]) > 0
+    for k in before[3]:
+        np.testing.assert_array_equal(after[3][k], before[3][k], err_msg=f"stamps of {k}")
+
+
 def _bench(args, env_extra=None, timeout=300):
     env = dict(os.environ, **(env_extra or {}))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], env=env, capture_output=True,

@@ -285,6 +285,50 @@ def test_gui_tree_check(tmp_path):
         assert r.returncode == 0 and r.stdout.strip() == "ok", f"{extra[0]}: " + r.stdout + r.stderr
 
 
+def test_model_build_check(tmp_path):
+    """The main path's host-only model building (psgpu_model_build.h: the walk program and the
+    DevModel image, PrepareBBoxes, the lattice, the cost split) from that header alone, with g++
+    and no ROCm include path: every input struct in an allocation of exactly its size, plain and
+    under ASan + UBSan.  The same table of cases then runs through the library's
+    psgpu_model_image, psgpu_prepare_bboxes, psgpu_mpu_dims and psgpu_split_costs.  All three
+    give the return codes and the bytes recorded from the library before the code moved
+    (tests/golden/model_build_cases.txt)."""
+    import shutil
+    import subprocess
+
+    gpp = shutil.which("g++")
+    if gpp is None:
+        pytest.skip("no g++")
+    gpu.load()
+    want = open(os.path.join(ROOT, "tests", "golden", "model_build_cases.txt")).read()
+    assert want.count("\n") > 50 and want.endswith("ok\n")
+    base = [gpp, "-std=c++17", "-O2", "-g", "-Wall", "-I", os.path.join(ROOT, "parsip_amd", "csrc"),
+            os.path.join(ROOT, "tests", "cpp", "model_build_check.cpp")]
+    lib_dir = os.path.join(ROOT, "parsip_amd")
+    builds = ([], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+              ["-DMODEL_BUILD_VIA_LIBRARY", "-L", lib_dir, "-l:libparsip_gpu.so", f"-Wl,-rpath,{lib_dir}"])
+    for k, extra in enumerate(builds):
+        exe = tmp_path / f"model_build_check{k}"
+        subprocess.run([*base, *extra, "-o", str(exe)], check=True)
+        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout == want, f"{extra[:1]}: " + r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_model_image_digests():
+    """gpu.model_image of every synth config and of the fuzz parity seeds, against the digests
+    recorded before the model builder moved into psgpu_model_build.h: every byte of the 28 KB
+    image matters (set_model's "same model", the graph key, the JIT cache)."""
+    import json
+
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_model_image_digests as mk
+
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "model_image_digests.json")))["models"]
+    got = {name: mk.digest(m) for name, m in mk.models()}
+    assert len(got) == len(synth.CONFIGS) + len(mk.FUZZ_SEEDS) and set(got) == set(want)
+    assert got == want, [n for n in got if got[n] != want[n]]
+
+
 def test_compile_slot(tmp_path):
     """The owner of a pending compile (psgpu_compile.h), from that header alone: start and drop
     never wait, poll hands a result out once, drain and the destructor wait for the pending job
