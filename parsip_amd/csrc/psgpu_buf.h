@@ -1,5 +1,6 @@
-// psgpu_buf.h — the owners of the library's device and pinned allocations (host only).
-// Every hipMalloc / hipHostMalloc of the library is made, and freed, here.
+// psgpu_buf.h — the owners of the library's device, pinned, stream and event handles (host only).
+// Every hipMalloc / hipHostMalloc, every stream and every event of the library is made, and
+// freed or destroyed, here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -106,6 +107,66 @@ struct PinnedBuf {
         if (ptr) (void)hipHostFree(ptr);
         ptr = nullptr;
         cap = 0;
+    }
+};
+
+// One stream, one event.  create() is a no-op while the handle is held; the same rule as DevBuf:
+// in a heap context, never static.  reset() wants the handle's device current.
+struct Stream {
+    hipStream_t h = nullptr;
+
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    Stream(Stream&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h = std::exchange(o.h, nullptr);
+        }
+        return *this;
+    }
+    ~Stream() { reset(); }
+    operator hipStream_t() const { return h; }
+
+    hipError_t create(unsigned flags) {
+        if (h) return hipSuccess;
+        const hipError_t e = hipStreamCreateWithFlags(&h, flags);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+    void reset() {
+        if (h) (void)hipStreamDestroy(h);
+        h = nullptr;
+    }
+};
+
+struct Event {
+    hipEvent_t h = nullptr;
+
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h = std::exchange(o.h, nullptr);
+        }
+        return *this;
+    }
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return h; }
+
+    hipError_t create(unsigned flags = hipEventDefault) {  // (hipEventCreate is these flags)
+        if (h) return hipSuccess;
+        const hipError_t e = hipEventCreateWithFlags(&h, flags);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+    void reset() {
+        if (h) (void)hipEventDestroy(h);
+        h = nullptr;
     }
 };
 

@@ -65,8 +65,7 @@ int export_stage(psgpu_ctx* c, bool mesh, bool stats, ExportStage* st, hipEvent_
         for (size_t i = 0, n = (c->hostStage.cap - flagBytes) / 4; i < n; ++i) w[i] = S.epoch;
     }
     hipStream_t s = c->stream;
-    for (hipEvent_t& e : c->exportEv)
-        if (!e) PSGPU_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event& e : c->exportEv) PSGPU_CHECK(e.create(hipEventDisableTiming));
     unsigned char* hd = nullptr;  // the staging as the device addresses it
     PSGPU_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd), h, 0));
     if (N) {

@@ -513,7 +513,7 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
         c->hostCtr.reserve(1, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hostCtrDev), c->hostCtr, 0) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+        c->stream.create(hipStreamNonBlocking) != hipSuccess) {
         psgpu_destroy(c);
         return PSGPU_RET_DEVICE_ERROR;
     }
@@ -526,7 +526,7 @@ int psgpu_create(int deviceOrdinal, psgpu_ctx** out) {
         psgpu_destroy(c);
         return PSGPU_RET_DEVICE_ERROR;
     }
-    for (int i = 0; i <= kNumKernels; ++i) (void)hipEventCreate(&c->ev[i]);
+    for (int i = 0; i <= kNumKernels; ++i) (void)c->ev[i].create();
     const char* cullEnv = getenv("PSGPU_CULL");
     if (cullEnv) c->cull = atoi(cullEnv) != 0;
     if (const char* e = getenv("PSGPU_OP_INSIDE")) c->opInside = atoi(e) != 0;
@@ -555,11 +555,9 @@ void psgpu_destroy(psgpu_ctx* c) {
     c->jit.compile.drain();
     c->jit.baked.drain();
     weld_state_free(c->weld);
-    for (int i = 0; i <= kNumKernels; ++i)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (hipEvent_t e : c->exportEv)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (Event& e : c->ev) e.reset();
+    for (Event& e : c->exportEv) e.reset();
+    c->stream.reset();  // ahead of the buffers
     delete c;  // its buffers go with it, on the device made current above
 }
 

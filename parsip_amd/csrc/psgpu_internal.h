@@ -1,6 +1,6 @@
 // psgpu_internal.h — the device context shared by the library's host sources
 // (psgpu_host.cpp: one context, psgpu_export.cpp: its blocking export, psgpu_group.cpp: contexts
-// over several devices and the multi-process count exchange).  Not part of the C-ABI.
+// over several devices, psgpu_comm.cpp: the multi-process count exchange).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -104,7 +104,7 @@ struct psgpu_ctx {
     uint64_t serial = 0;  // process-unique id: this context's PrintThreadResults entry
     bool countThreads = true;  // finished runs add to that entry (off for a group's planning runs)
     int numCUs = 256;
-    hipStream_t stream = nullptr;
+    psgpu::Stream stream;
     PsSoaBlobPrims primsHost;  // bbox + counts of the current model
     DevModel model{};
     psgpu::DevBuf<DevModel> dModel;
@@ -128,7 +128,7 @@ struct psgpu_ctx {
     float cs = 0.0f;
     uint32_t dims[3] = {0, 0, 0};
     uint32_t mpuBegin = 0, mpuCount = 0;
-    hipStream_t runStream = nullptr;
+    hipStream_t runStream = nullptr;  // borrowed: the caller's, or `stream`
     bool pending = false;
     bool haveResult = false;
     // device buffers
@@ -169,12 +169,12 @@ struct psgpu_ctx {
     psgpu::PinnedBuf<DevCounters> hostCtr;  // pinned, mapped: written by k_finish
     DevCounters* hostCtrDev = nullptr;  // its device address
     psgpu::PinnedBuf<unsigned char> hostStage;  // pinned staging for the blocking PolyMPUs export
-    hipEvent_t exportEv[2] = {};         // the export's metadata, then its packing kernel
+    psgpu::Event exportEv[2];            // the export's metadata, then its packing kernel
     uint32_t exportEpoch = 0;            // the blocking export's flag value (k_export_pack), never 0
     std::unique_ptr<psgpu::ScatterPool> scatterPool;  // the export's scatter threads, made on first use
     uint32_t vcap = 1u << 20, tcap = 1u << 21;               // compact mesh capacity
     uint32_t vShardCap = 1u << 15, tShardCap = 1u << 16;      // work-queue capacity per shard
-    hipEvent_t ev[kNumKernels + 1] = {};
+    psgpu::Event ev[kNumKernels + 1];
     int useGraph = 0;  // replay repeated launch sequences from a hipGraph (measured slower on ROCm 7.2)
     struct GraphSlot {
         hipGraphExec_t exec = nullptr;

@@ -6,17 +6,19 @@
 
 #include <algorithm>
 
+#include "psgpu_buf.h"
+
 namespace psgpu {
 
 // The events a shared launch sequence records, in order (PhaseTimes::rest); none when untimed.
 struct PhaseCursor {
-    hipEvent_t* ev = nullptr;
+    Event* ev = nullptr;
     hipError_t mark(hipStream_t s) { return ev ? hipEventRecord(*ev++, s) : hipSuccess; }
 };
 
 template <int N>
 struct PhaseTimes {
-    hipEvent_t ev[N] = {};  // before the first step, after each; made by the first timed call
+    Event ev[N];            // before the first step, after each; made by the first timed call
     float ms[N] = {};       // the last call's: the whole, then each step (0: untimed, or it launched nothing)
     bool timed = false;     // the call in progress records events; `next` is the first it has not
     int next = 0;
@@ -29,16 +31,16 @@ struct PhaseTimes {
     // A call begins; the events' device is current.
     hipError_t begin(bool on) {
         clear();
-        for (hipEvent_t& e : ev)
-            if (on && !e) {
-                const hipError_t err = hipEventCreate(&e);
+        for (Event& e : ev)
+            if (on) {
+                const hipError_t err = e.create();
                 if (err != hipSuccess) return err;
             }
         timed = on;
         return hipSuccess;
     }
     hipError_t mark(hipStream_t s) { return timed ? hipEventRecord(ev[next++], s) : hipSuccess; }
-    hipEvent_t take() { return timed ? ev[next++] : nullptr; }  // for a callee that records one event itself
+    hipEvent_t take() { return timed ? ev[next++].h : nullptr; }  // for a callee that records one event itself
     PhaseCursor rest() { return PhaseCursor{timed ? ev + next : nullptr}; }  // ... or all that remain
     // The call's stream has been waited for and every event recorded.
     void collect() {
@@ -55,10 +57,7 @@ struct PhaseTimes {
         return n;
     }
     void free() {
-        for (hipEvent_t& e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+        for (Event& e : ev) e.reset();
         clear();
     }
 };

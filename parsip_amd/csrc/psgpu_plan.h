@@ -21,6 +21,7 @@
 #include <numeric>
 
 #include "../../include/parsip_gpu.h"
+#include "psgpu_group_plan.h"
 #include "psgpu_model.h"
 
 namespace psgpu {
@@ -327,7 +328,7 @@ inline PsMeshInfo mesh_info(const DevCounters& h, const LaunchPlan& run, uint32_
     I.ctTriangles = mpuCount ? sum.t : 0;
     I.firstOverflowMPU = (mpuCount && h.firstOverflow != 0x7fffffff) ? h.firstOverflow : -1;
     I.ctFieldMPUs = mpuCount ? sum.p : 0;
-    I.ctLaneEvals = 8ull * mpuCount + 512ull * I.ctFieldMPUs + 8ull * I.ctVertices;
+    I.ctLaneEvals = lane_evals(mpuCount, I.ctFieldMPUs, I.ctVertices);
     I.launchFlags = mpuCount == 0 ? 0u
                     : (run.split ? PSGPU_LAUNCH_TREE_SPLIT : 0u) | (run.surface ? PSGPU_LAUNCH_SURFACE : 0u) |
                           (run.front ? PSGPU_LAUNCH_FRONT : 0u) | (reran ? PSGPU_LAUNCH_RERUN : 0u) |

@@ -100,6 +100,32 @@ def test_group_on_one_device_returns_every_byte():
     assert gpu.device_bytes() == base
 
 
+def test_group_gather_and_weld_move_between_parts_on_live_streams():
+    """The group's gathered mesh and its weld are each torn down and rebuilt on another part while
+    the gather stream and the timing events are in use: gather and timed weld on part 0, shells,
+    the weld again on part 1 (same bytes), the gather back on part 0, destroy.  Two devices where
+    there are two, else two parts on one."""
+    base = gpu.device_bytes()
+    g = gpu.Group([0, 1] if gpu.device_count() > 1 else [0, 0])
+    try:
+        model, cs, _ = make_case(NAME)
+        g.set_option(gpu.OPT_KERNEL_TIMING, 1)
+        g.set_model(model)
+        info, _ = g.run(cs)
+        assert g.gather(0).pos
+        first = g.weld(dst_part=0)
+        assert first.info.ctInputVertices == info.ctVertices > 0
+        assert g.weld_times()["group weld total"] > 0
+        assert g.weld_shells().info["ctShells"] > 0
+        assert weld_bytes(g.weld(dst_part=1)) == weld_bytes(first)
+        assert g.weld_times()["group weld total"] > 0
+        assert g.gather(0).pos
+        assert gpu.device_bytes() > base
+    finally:
+        g.close()
+    assert gpu.device_bytes() == base
+
+
 def test_compat_context_returns_every_byte():
     base = gpu.device_bytes()
     _, small = gui.compact_blobtree(_pcm_pair())

@@ -242,6 +242,42 @@ def test_rccl_exchange_single_rank(gpu_poly):
         comm.close()
 
 
+_COUNTS = ("ctMPUs", "ctVertices", "ctTriangles", "ctPassedPrecheck", "ctSurfaceMPUs", "ctFieldMPUs",
+           "firstOverflowMPU", "ctLaneEvals")
+
+
+@pytest.mark.parametrize("comm_first", [True, False], ids=["comm_closed_first", "groups_closed_first"])
+def test_rccl_exchange_group_changing_part_count_single_rank(comm_first):
+    """One communicator at world size 1 exchanges a two-part group's run, then a three-part
+    group's (its per-part events grow), then a plain context's; each result equals the finish of
+    what ran.  The communicator owns the events and the summed totals, so it may be closed before
+    the groups or after them: either way every device byte comes back."""
+    model, cs, _ = synth.make_config("C2")
+    base = gpu.device_bytes()
+    runners = [gpu.Group([0, 0]), gpu.Group([0, 0, 0]), gpu.Polygonizer(0)]
+    comm = gpu.Comm(runners[2], gpu.comm_unique_id(), 1, 0)
+    try:
+        for r in runners:
+            is_group = isinstance(r, gpu.Group)
+            comm._poly, comm._group = r, r if is_group else None  # what exchange() sends
+            r.set_model(model)
+            r.polygonize(cs)
+            comm.exchange()
+            total, parts = comm.result()
+            assert not comm.reexchanged()
+            info = r.finish()[0] if is_group else r.finish()
+            assert info.ctVertices > 0
+            assert [getattr(total, k) for k in _COUNTS] == [getattr(info, k) for k in _COUNTS]
+            assert (parts[0].device, parts[0].mpuBegin, parts[0].mpuEnd, parts[0].vertexBase, parts[0].triangleBase) == \
+                (0, 0, info.ctMPUs, 0, 0)
+            assert [getattr(parts[0].info, k) for k in _COUNTS] == [getattr(info, k) for k in _COUNTS]
+        assert gpu.device_bytes() > base
+    finally:
+        for x in ([comm] + runners) if comm_first else (runners + [comm]):
+            x.close()
+    assert gpu.device_bytes() == base
+
+
 def test_rccl_exchange_after_rerun_single_rank(gpu_poly):
     """A run whose k_mpu grid fell short (test hook: debug bit 20, one block) exchanges
     incomplete totals; finish() re-runs it with the full grid, the ranks agree on a second

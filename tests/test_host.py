@@ -314,6 +314,30 @@ def test_model_build_check(tmp_path):
         assert r.returncode == 0 and r.stdout == want, f"{extra[:1]}: " + r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_group_plan_check(tmp_path):
+    """What a group decides without a GPU (psgpu_group_plan.h: the even split and its active
+    parts, when polygonize re-splits and finishes the pending run first, the decoding of the 8
+    k_finish words, the parts' places in the whole mesh and its 2^32 limits) from the headers
+    alone, with g++ and no ROCm include path: every array in an allocation of exactly its size,
+    plain and under ASan + UBSan.  Both give the lines recorded from the bodies of
+    psgpu_group.cpp's entry points before the code moved (tests/golden/group_plan_cases.txt)."""
+    import shutil
+    import subprocess
+
+    gpp = shutil.which("g++")
+    if gpp is None:
+        pytest.skip("no g++")
+    want = open(os.path.join(ROOT, "tests", "golden", "group_plan_cases.txt")).read()
+    assert want.count("\n") > 200 and want.endswith("ok\n")
+    base = [gpp, "-std=c++17", "-O2", "-g", "-Wall", "-I", os.path.join(ROOT, "parsip_amd", "csrc"),
+            os.path.join(ROOT, "tests", "cpp", "group_plan_check.cpp")]
+    for k, extra in enumerate(([], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = tmp_path / f"group_plan_check{k}"
+        subprocess.run([*base, *extra, "-o", str(exe)], check=True)
+        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout == want, f"{extra[:1]}: " + r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_model_image_digests():
     """gpu.model_image of every synth config and of the fuzz parity seeds, against the digests
     recorded before the model builder moved into psgpu_model_build.h: every byte of the 28 KB
