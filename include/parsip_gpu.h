@@ -475,6 +475,16 @@ int  psgpu_mpu_masks(psgpu_ctx* ctx, uint8_t* queued, uint64_t* masks, uint32_t 
  * their number (0 when the run took no sieve: PSGPU_LAUNCH_SIEVE), bricks (may be null) 3 words
  * per brick, its lattice brick coordinates (x, y, z: MPU coordinates / 2). */
 int  psgpu_live_bricks(psgpu_ctx* ctx, uint32_t* bricks, uint32_t capacity, uint32_t* count);
+/* Debug export of the finished run's count of S2 passes: S2 walks each queued MPU's octants that
+ * S1's field bounds left undecided, 4 octants per pass (0, 1 or 2 passes per MPU).  Counted only
+ * in a run with PSGPU_OPT_DEBUG bit 9 (512) set; 0 otherwise, and for the tree-split kernels,
+ * which walk every octant.  With bit 7 (128) S2 treats every octant as undecided: 2 per MPU. */
+int  psgpu_s2_passes(psgpu_ctx* ctx, uint32_t* passes);
+/* Debug export of the finished run's S1 octant verdicts, read from its queue entries: for each of
+ * the range's ctMPUs, oct[w] = bit c: octant c (xh | yh << 1 | zh << 2) of the MPU proven outside,
+ * bit 8 + c: proven inside; 0 for an MPU that was not queued for S2.  The tree-split S1 writes
+ * them too, though its S2 does not read them.  capacity is in MPUs. */
+int  psgpu_mpu_octants(psgpu_ctx* ctx, uint16_t* oct, uint32_t capacity);
 /* Device memory the library holds at this moment, in bytes, over every context, group, comm
  * and compatibility context of the process (pinned host memory is not counted).  Exact, unlike
  * a device's free memory, which other processes change: a leak test compares two readings. */

@@ -779,9 +779,13 @@ __device__ __forceinline__ BoundBox octant_box(const Params& p, const float o[3]
 }
 
 // The lanes' octant intervals -> bit g: MPU g passed S1 (flags8) and all 8 of its octants are
-// proven outside (hi < 0.5) or all 8 inside (lo >= 0.5): no surface, 0 V / 0 T without S2
-__device__ __forceinline__ uint32_t proven_mask(bool ok, float lo, float hi, uint32_t flags8) {
+// proven outside (hi < 0.5) or all 8 inside (lo >= 0.5): no surface, 0 V / 0 T without S2.
+// The two ballots stay (oct[0]: outside, oct[1]: inside; bit 8g + c: octant c of MPU g): a queued
+// MPU's 16 bits go with its queue entry, and S2 walks only its undecided octants.
+__device__ __forceinline__ uint32_t proven_mask(bool ok, float lo, float hi, uint32_t flags8, uint64_t oct[2]) {
     const uint64_t bOut = ballot(ok && hi < 0.5f), bIn = ballot(ok && lo >= 0.5f);
+    oct[0] = bOut;
+    oct[1] = bIn;
     uint32_t proven8 = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -838,7 +842,9 @@ __device__ __forceinline__ CullMask queue_masks(const Params& p, const CullLanes
     return mine;
 }
 
-// A queued MPU as S1 hands it to S2: its global id in pq[slotq] and four mask words in
+// A queued MPU as S1 hands it to S2: in pq[slotq] its global id and, above it, the verdicts of
+// S1's field bounds on its 8 octants (oct: bit c proven outside, bit 8 + c proven inside; zero
+// without bounds; one 64-bit word, so they cost no memory instruction), and four mask words in
 // pqMask[4 * slotq ..] (the MPU box's culling mask and op-inside mask, from queue_masks; not
 // written and not read without culling).  Between launches (k_precheck, then k_mpu) plain
 // stores and loads.  Within k_front's one launch (FRONT; MI355X_MICROARCH.md hand-off table,
@@ -851,6 +857,7 @@ __device__ __forceinline__ CullMask queue_masks(const Params& p, const CullLanes
 struct QueueEntry {
     uint32_t m;
     CullMask cm;
+    uint32_t oct;  // S1's verdicts on the MPU's octants: bit c proven outside, bit 8 + c proven inside
 
     template <bool FRONT, class T>
     static __device__ __forceinline__ void put(T* at, T v) {
@@ -864,7 +871,7 @@ struct QueueEntry {
     }
     template <bool FRONT>
     __device__ __forceinline__ void store(const Params& p, uint32_t slotq) const {
-        put<FRONT>(&p.pq[slotq], m);
+        put<FRONT>(&p.pq[slotq], (uint64_t)m | ((uint64_t)oct << 32));
         if (p.cull) {
             put<FRONT>(&p.pqMask[4 * slotq], cm.lo);
             put<FRONT>(&p.pqMask[4 * slotq + 1], cm.hi);
@@ -881,7 +888,8 @@ struct QueueEntry {
     // skip of an op-box pruning test of the S2 walk is a scalar branch
     template <bool FRONT>
     static __device__ __forceinline__ QueueEntry load(const Params& p, ModelPtr M, uint32_t slotq) {
-        QueueEntry e{uniform(get<FRONT>(&p.pq[slotq])), CullMask{0ull, 0ull}};
+        const uint64_t id = uniform64(get<FRONT>(&p.pq[slotq]));
+        QueueEntry e{(uint32_t)id, CullMask{0ull, 0ull}, (uint32_t)(id >> 32)};
         if (p.cull) {
             e.cm.lo = uniform64(get<FRONT>(&p.pqMask[4 * slotq]));
             e.cm.hi = uniform64(get<FRONT>(&p.pqMask[4 * slotq + 1]));
@@ -998,6 +1006,7 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     for (int q = 0; q < 8; ++q) flags8 |= (((bal >> (8 * q)) & 0xffull) != 0ull ? 1u : 0u) << q;
     // survivors proven empty by field bounds; the wave's culling box covers every MPU of the brick
     uint32_t proven8 = 0;
+    uint64_t oct[2] = {0ull, 0ull};  // the octants proven outside / inside (proven_mask); zero without bounds
     float lo = 0.0f, hi = 0.0f;  // the lane's interval over its octant
     bool ok = true;
     if ((p.debug & 1024u) && flags8 != 0u) __builtin_amdgcn_s_setprio(2);  // experiment: heavy waves first
@@ -1019,11 +1028,11 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
             const int r = slot * 2, l = slot * 2 + 1;
             ok = sOk[r][lane] != 0u && sOk[l][lane] != 0u;
             ev.bound_combine(sLo[r][lane], sHi[r][lane], sLo[l][lane], sHi[l][lane], cm, &lo, &hi);
-            proven8 = proven_mask(ok, lo, hi, flags8);
+            proven8 = proven_mask(ok, lo, hi, flags8, oct);
         }
     } else if (p.bound && flags8 != 0u) {
         ev.bound(octant_box(p, o, c), cm, &lo, &hi, &ok);
-        proven8 = proven_mask(ok, lo, hi, flags8);
+        proven8 = proven_mask(ok, lo, hi, flags8, oct);
         phase_stamp(p, 2, 8192u);
     }
     const uint32_t queue8 = flags8 & ~proven8;
@@ -1049,19 +1058,19 @@ __device__ __forceinline__ void precheck_body(const Params& p, float* lds) {
     // made (their round trip overlaps the mask computation; verdict r05 item 4)
     uint32_t baseAtomic = 0;
     if (lane == 0) baseAtomic = atomicAdd(&p.ctr->shard[qsel].p, (uint32_t)__popc(queue8));
-    const QueueEntry e{mOf, queue_masks(p, cl, o, queue8, mOf, lane)};  // lane q < 8: MPU q's entry
+    QueueEntry e{mOf, queue_masks(p, cl, o, queue8, mOf, lane), 0u};  // lane q < 8: MPU q's entry
     asm volatile("" : "+v"(baseAtomic) : "v"(e.cm.lo));  // the wait for the atomic goes here
     const uint32_t base = lane_value(baseAtomic, 0);
     const uint32_t slotq = pass ? qbase + base + (uint32_t)__popc(queue8 & ((1u << lane) - 1u)) : 0u;
+    int sh = lane;  // (taken here, after the masks: made earlier, the shift is one more register across them)
+    asm volatile("" : "+v"(sh) : "v"(e.cm.lo));
+    sh = 8 * (sh & 7);  // lane q < 8: MPU q's octants, proven outside | proven inside << 8
+    e.oct = (uint32_t)((oct[0] >> sh) & 0xffull) | ((uint32_t)((oct[1] >> sh) & 0xffull) << 8);
     if (pass) e.template store<FRONT>(p, slotq);
     phase_stamp(p, 3, 8192u);
     if constexpr (FRONT) QueueEntry::publish(p, slotq, pass);
 }
 
-#ifndef PSGPU_S2_N
-#define PSGPU_S2_N 8  // x-slices per walk: one walk per (y,z) needle shares each primitive's
-                      // uniform work and (y,z) terms over its points
-#endif
 // LDS per k_mpu block: one MpuLds per MPU of the block (4, or 2 with the tree split), then per
 // wave the interpreter's value slots.  The S2 field values never leave registers: pass 1 needs
 // only their inside bits (8 ballots, shared by the MPU's waves through LDS).
@@ -1142,51 +1151,101 @@ __device__ __forceinline__ auto s2_parts() -> float (*)[8][64] {
 // S2 (:550-610), block-level: every wave of the block calls it, with or without an MPU (live),
 // and meets the one barrier in it (mpu_sync: the block's when the tree split gives an MPU two
 // waves), between phase stamps 3 and 4.  Before it the wave's walk of the 8x8x8 corner cache of
-// the MPU at o: lane = y*8 + z, the 8 x-slices per lane; quads = 4 consecutive z.  The field
-// values never leave registers: pass 1 needs only their inside bits, ins[x] bit y*8 + z (lane
-// order), which go through the MPU's sIns; with the tree split the wave walks subtree `wave %
-// SPLIT` of the root, the two parts' values go through LDS and both waves combine and ballot
-// them.  Returns the count of inside corners; ins[] is zero without an MPU.
+// the MPU at o.  The field values never leave registers: pass 1 needs only their inside bits,
+// ins[x] bit y*8 + z, which go through the MPU's sIns.
+// One wave per MPU (SPLIT 1): only the octants S1's field bounds left undecided are walked
+// (`oct`, the entry's: bit c proven outside, bit 8 + c proven inside; s2_plan_octant,
+// psgpu_model.h): per pass 4 octants, 16 lanes each (lane & 3 = z', (lane >> 2) & 3 = y', the 4 x
+// per lane: quads = 4 consecutive z at one (x, y), as in the full walk), one evaln<.., 4> in a
+// run-time loop, so the walk's code exists once.  sIns takes the decided octants' bits as
+// constants, then each pass ORs in its octants' ballots (lane 4g + n: group g's 16 bits of x
+// n), all before the barrier.  PSGPU_OPT_DEBUG bit 7: every octant counts as undecided (two
+// passes, all 512 corners); bit 9: the passes are counted (DevCounters::s2Passes).
+// With the tree split (lane = y*8 + z, the 8 x-slices per lane; the verdicts are ignored: its
+// launches are small shares where S1 weighs more) the wave walks subtree `wave % SPLIT` of the
+// root, the two parts' values go through LDS and both waves combine and ballot them.
+// Returns the count of inside corners; ins[] is zero without an MPU.
 template <class EV, int SPLIT>
 __device__ __forceinline__ uint32_t block_s2_inside_bits(EV& ev, const Params& p, bool live, const float o[3],
-                                                         const CullMask& cm, int wave, uint64_t* sIns,
+                                                         const CullMask& cm, uint32_t oct, int wave, uint64_t* sIns,
                                                          uint64_t ins[8]) {
-    constexpr int NX = 8;  // x-slices of the S2 cache, all walked by this wave
+    constexpr int NX = 8;  // x-slices of the S2 cache
     const int lane = lane_id();
-    float fs[NX];
+    float fs[SPLIT > 1 ? NX : 4];  // the values of one walk: 8 x-slices, or the 4 x of an octant
     if (live) {
         const float cs = p.cs;
-        const int y = lane >> 3, z = lane & 7;
-        const float py = o[1] + (float)y * cs;
-        const float pz = o[2] + (float)z * cs;
         phase_stamp(p, 2);
-        float pxs[NX], pys[NX], pzs[NX];
-#pragma unroll
-        for (int x = 0; x < NX; ++x) {
-            pxs[x] = o[0] + (float)x * cs;
-            pys[x] = py;
-            pzs[x] = pz;
-        }
         if constexpr (SPLIT > 1) {
+            const int y = lane >> 3, z = lane & 7;
+            const float py = o[1] + (float)y * cs;
+            const float pz = o[2] + (float)z * cs;
+            float pxs[NX], pys[NX], pzs[NX];
+#pragma unroll
+            for (int x = 0; x < NX; ++x) {
+                pxs[x] = o[0] + (float)x * cs;
+                pys[x] = py;
+                pzs[x] = pz;
+            }
             if (wave % SPLIT == 0) ev.template evaln_part<4, false, 8, 0>(pxs, pys, pzs, cm, fs, nullptr);
             else ev.template evaln_part<4, false, 8, 1>(pxs, pys, pzs, cm, fs, nullptr);
 #pragma unroll
             for (int x = 0; x < NX; ++x) s2_parts()[wave][x][lane] = fs[x];
         } else {
-#if PSGPU_S2_N == 1
-            // one walk per x-slice in a runtime loop: the walk's code stays resident in the
-            // instruction cache (unrolled copies of a 32-primitive walk do not fit)
+            const uint32_t all = (p.debug & 128u) ? 0u : 0xffffu;  // ablation: no verdict is used
+            const uint32_t inside8 = (oct & all) >> 8, known = ((oct & all) | inside8) & 0xffu;
+            if (lane < NX) sIns[lane] = s2_inside_const(inside8, (uint32_t)lane >> 2);
+            mpu_sync<1>();  // the wave's constants are in place before its ORs
+            const uint32_t passes = s2_pass_count(known);
+            if ((p.debug & 512u) && lane == 0) atomicAdd(&p.ctr->s2Passes, passes);
+            // The lane's plan, 8 bits per pass, in one vector register across the walks: its
+            // octant, the octant of lane group lane >> 2 (lanes < 16: the ORs), that group
+            // walks an octant of its own, another pass follows.  With the origin and the cell
+            // size beside it the loop holds no scalar but the walk's own, and the walk's inputs
+            // (the masks, as scalars, and the model's address) are opaque to the compiler in
+            // each pass, so that its uniform tests and loads are made again per pass: hoisted
+            // out of the loop they are all live across it (128-170 spilled SGPRs, C3 and C5).
+            const uint32_t g16 = ((uint32_t)lane & 12u) << 2;  // first lane of group lane >> 2
+            uint32_t plan = 0u;
+#pragma unroll
+            for (uint32_t t = 0; t < 2u; ++t)
+                if (t < passes)
+                    plan |= (s2_plan_octant(known, t, (uint32_t)lane) | (s2_plan_octant(known, t, g16) << 3) |
+                             ((s2_group_walks(known, t, g16) ? 1u : 0u) << 6) | ((t + 1u < passes ? 1u : 0u) << 7))
+                            << (8u * t);
+            float ox = o[0], oy = o[1], oz = o[2], csv = cs;
+            CullMask cml{uniform64(cm.lo), uniform64(cm.hi), uniform64(cm.inLo), uniform64(cm.inHi)};
+            EV evl = ev;
+            bool more = passes != 0u;
 #pragma unroll 1
-            for (int h = 0; h < NX; ++h) fs[h] = ev.template eval<4, false>(pxs[h], py, pz, cm, nullptr);
-#else
+            while (more) {
+                asm volatile("" : "+v"(plan), "+v"(ox), "+v"(oy), "+v"(oz), "+v"(csv));
+                asm volatile("" : "+s"(cml.lo), "+s"(cml.hi), "+s"(cml.inLo), "+s"(cml.inHi), "+s"(evl.M));
+                const uint32_t c = plan & 7u;
+                const int y = 4 * (int)((c >> 1) & 1u) + ((lane >> 2) & 3), z = 4 * (int)(c >> 2) + (lane & 3);
+                const float py = oy + (float)y * csv;
+                const float pz = oz + (float)z * csv;
+                float pxs[4], pys[4], pzs[4];
 #pragma unroll
-            for (int h = 0; h < NX; h += PSGPU_S2_N)
-                ev.template evaln<4, false, PSGPU_S2_N>(pxs + h, pys + h, pzs + h, cm, fs + h, nullptr);
-#endif
+                for (int n = 0; n < 4; ++n) {
+                    pxs[n] = ox + (float)(4 * (int)(c & 1u) + n) * csv;
+                    pys[n] = py;
+                    pzs[n] = pz;
+                }
+                evl.template evaln<4, false, 4>(pxs, pys, pzs, cml, fs, nullptr);
+                uint64_t b = 0ull;  // lane 4g + n: the ballot of x n, for group g's 16 bits
 #pragma unroll
-            for (int x = 0; x < NX; ++x) {
-                const uint64_t b = ballot(fs[x] >= 0.5f);
-                if (lane == 0) sIns[x] = b;
+                for (int n = 0; n < 4; ++n) {
+                    const uint64_t bn = ballot(fs[n] >= 0.5f);
+                    if ((lane & 3) == n) b = bn;
+                }
+                if (lane < 16 && ((plan >> 6) & 1u)) {
+                    const uint32_t cg = (plan >> 3) & 7u;
+                    const uint64_t bits = s2_spread((uint32_t)(b >> g16) & 0xffffu, cg);
+                    __hip_atomic_fetch_or(&sIns[4u * (cg & 1u) + ((uint32_t)lane & 3u)], bits, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                more = uniform((plan >> 7) & 1u) != 0u;
+                plan >>= 8;
             }
         }
     }
@@ -1433,7 +1492,7 @@ __device__ __forceinline__ void mpu_body(const Params& p, unsigned char* smem, u
     MpuLds& L = *reinterpret_cast<MpuLds*>(smem + slot * kLdsMpu);
     EV ev(M, reinterpret_cast<float*>(smem + kLdsWaveSlots + wave * p.slotsPerLane * 64 * 4) + lane);
     uint64_t ins[8];  // (block-level: the S2 barrier is in it)
-    const uint32_t inside = block_s2_inside_bits<EV, SPLIT>(ev, p, live, o, e.cm, wave, L.ins, ins);
+    const uint32_t inside = block_s2_inside_bits<EV, SPLIT>(ev, p, live, o, e.cm, e.oct, wave, L.ins, ins);
     const bool work = live && inside != 0 && inside != 512 && !(p.debug & 1u);
     if (live && !work && part == 0 && lane == 0) p.counts[w] = 0ull;  // no vertices, no triangles
 

@@ -868,6 +868,39 @@ int psgpu_live_bricks(psgpu_ctx* c, uint32_t* bricks, uint32_t capacity, uint32_
     return PSGPU_RET_SUCCESS;
 }
 
+int psgpu_mpu_octants(psgpu_ctx* c, uint16_t* oct, uint32_t capacity) {
+    if (!c || !oct) return PSGPU_RET_PARAM_ERROR;
+    int rc = finished_run(c);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    if (c->mpuCount > capacity) return PSGPU_RET_PARAM_ERROR;
+    for (uint32_t w = 0; w < c->mpuCount; ++w) oct[w] = 0;
+    if (c->mpuCount == 0) return PSGPU_RET_SUCCESS;
+    // k_front: 8 sub-queues of fqCap entries; otherwise the kShards queues of pShardCap
+    const uint32_t queues = c->run.front ? 8u : (uint32_t)kShards, cap = c->run.front ? c->run.fqCap : c->pShardCap;
+    std::vector<uint64_t> q;
+    for (uint32_t k = 0; k < queues; ++k) {
+        const uint32_t n = c->hostCtr->shard[k].p;
+        if (n == 0) continue;
+        if (n > cap || (size_t)k * cap + n > c->pq.cap) return PSGPU_RET_DEVICE_ERROR;
+        q.resize(n);
+        PSGPU_CHECK(hipMemcpy(q.data(), c->pq + (size_t)k * cap, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t e : q) {
+            const uint32_t w = (uint32_t)e - c->mpuBegin;
+            if (w >= c->mpuCount) return PSGPU_RET_DEVICE_ERROR;
+            oct[w] = (uint16_t)(e >> 32);
+        }
+    }
+    return PSGPU_RET_SUCCESS;
+}
+
+int psgpu_s2_passes(psgpu_ctx* c, uint32_t* passes) {
+    if (!c || !passes) return PSGPU_RET_PARAM_ERROR;
+    int rc = finished_run(c);
+    if (rc != PSGPU_RET_SUCCESS) return rc;
+    *passes = c->mpuCount ? c->hostCtr->s2Passes : 0u;
+    return PSGPU_RET_SUCCESS;
+}
+
 int psgpu_download_spans(psgpu_ctx* c, uint64_t* out, uint32_t* runs) {
     if (!c || !runs) return PSGPU_RET_PARAM_ERROR;
     *runs = c->spans ? c->spanNext : 0u;

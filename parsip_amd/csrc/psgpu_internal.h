@@ -132,7 +132,7 @@ struct psgpu_ctx {
     bool pending = false;
     bool haveResult = false;
     // device buffers
-    psgpu::DevBuf<uint32_t> pq;         // sharded S1 survivor queues
+    psgpu::DevBuf<uint64_t> pq;         // sharded S1 survivor queues (id | octant verdicts << 32)
     psgpu::DevBuf<uint64_t> pqMask;     // 4 words per queue entry (culling and op-inside mask of the MPU box)
     psgpu::DevBuf<uint64_t> liveList;   // k_sieve's list of live bricks (one word per brick of the range)
     uint32_t pShardCap = 0;

@@ -563,6 +563,40 @@ inline bool root_zero_set(const DevModel& M, uint64_t m[2]) {
 }
 #endif
 
+// ---- S2 octant plan (DESIGN.md §4 "S2 octants").  S1's field bounds decide some of a queued
+// MPU's 8 octants (4x4x4 corners each; octant c = xh | yh << 1 | zh << 2, as octant_box has it):
+// `known` has bit c set when octant c is proven outside or inside.  S2 walks the others, 4 per
+// pass in octant order: 16 lanes per octant, lane & 3 = z', (lane >> 2) & 3 = y', the 4 x of the
+// octant per lane, so a quad of lanes is 4 consecutive z at one (x, y) -- the quads of the full
+// walk's lane = y * 8 + z layout, which is what op-box pruning groups by.
+PSGPU_HDI uint32_t s2_pass_count(uint32_t known) { return (8u - (uint32_t)__builtin_popcount(known & 0xffu) + 3u) >> 2; }
+// The octant lane group lane >> 4 walks in pass `pass` (< s2_pass_count): undecided octant
+// 4 * pass + (lane >> 4) in octant order; a group past the last one repeats the pass's first
+// octant (real points; its bits are dropped: s2_group_walks).
+PSGPU_HDI uint32_t s2_plan_octant(uint32_t known, uint32_t pass, uint32_t lane) {
+    uint32_t u = ~known & 0xffu;
+    for (uint32_t i = 0; i < 4u * pass; ++i) u &= u - 1u;
+    uint32_t v = u;
+    for (uint32_t i = 0; i < 3u; ++i)
+        if (i < (lane >> 4)) v &= v - 1u;
+    return (uint32_t)__builtin_ctz((v ? v : u) | 0x100u) & 7u;
+}
+PSGPU_HDI bool s2_group_walks(uint32_t known, uint32_t pass, uint32_t lane) {
+    return 4u * pass + (lane >> 4) < 8u - (uint32_t)__builtin_popcount(known & 0xffu);
+}
+// The inside bits ins[x] (bit y * 8 + z) of the x-slices of half xh, from the octants proven inside
+PSGPU_HDI uint64_t s2_inside_const(uint32_t inside8, uint32_t xh) {
+    uint64_t r = 0ull;
+    for (uint32_t c = xh; c < 8u; c += 2u)
+        if ((inside8 >> c) & 1u) r |= 0x0f0f0f0full << (32u * ((c >> 1) & 1u) + 4u * (c >> 2));
+    return r;
+}
+// A walked octant's 16 ballot bits of one x (bit 4 y' + z') at their place in ins[x]
+PSGPU_HDI uint64_t s2_spread(uint32_t w16, uint32_t c) {
+    const uint32_t r = (w16 & 0xfu) | ((w16 & 0xf0u) << 4) | ((w16 & 0xf00u) << 8) | ((w16 & 0xf000u) << 12);
+    return (uint64_t)r << (32u * ((c >> 1) & 1u) + 4u * (c >> 2));
+}
+
 // Compact-mesh work records written by the MPU kernel.
 // A vertex record in two arrays, so that each kernel moves only what it uses: k_mpu writes
 // the key (8 B), k_vertex reads it and writes the root (8 B), k_finish reads both and
@@ -611,7 +645,9 @@ struct DevCounters {
     uint32_t epoch;          // run sequence number: the previous run's last kernel sets it to its own
                              // + 1 when it resets this set; k_front tags its queue entries with it + 1
     uint32_t liveBricks;     // k_sieve: bricks appended to the live list (Params::liveList)
-    uint32_t pad[26];
+    uint32_t s2Passes;       // S2 passes walked (s2_pass_count summed over the queued MPUs); counted only
+                             // with PSGPU_OPT_DEBUG bit 9, otherwise 0
+    uint32_t pad[25];
     ShardCtr shard[kShards];
 };
 
@@ -643,7 +679,8 @@ struct Params {
     uint64_t* liveList;     // k_sieve: the bricks some primitive reaches, bi | bj << 21 | bk << 42
                             // (lattice brick coordinates), ctr->liveBricks of them, in any order
     uint32_t brickMagic[2]; // floor((2^32 - 1) / d) for d = brickDims[2], brickDims[1] * brickDims[2]
-    uint32_t* pq;           // kShards queues of pShardCap S1 survivors (global MPU ids)
+    uint64_t* pq;           // kShards queues of pShardCap S1 survivors: global MPU id | its octants
+                            // S1 proved outside << 32 | proved inside << 40 (QueueEntry)
     uint64_t* pqMask;       // per queue entry: the MPU box's culling mask (2 words) and its op-inside
                             // mask (2 words, op_inside_box), by k_precheck
     uint32_t pShardCap;     // 8 * ceil(precheck waves / kShards): cannot overflow

@@ -117,7 +117,8 @@ EXPORTED_SYMBOLS = [
     "psgpu_comm_reexchanged", "psgpu_polygonize_mpus_ex", "psgpu_download_process_stats",
     "psgpu_print_thread_results", "psgpu_thread_result_count",
     "psgpu_weld", "psgpu_weld_device", "psgpu_download_weld", "psgpu_weld_times",
-    "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks", "psgpu_debug_device_bytes",
+    "psgpu_vertex_queue", "psgpu_mpu_masks", "psgpu_live_bricks", "psgpu_s2_passes", "psgpu_mpu_octants",
+    "psgpu_debug_device_bytes",
     "psgpu_group_weld", "psgpu_group_weld_device", "psgpu_group_download_weld", "psgpu_group_weld_times",
     "psgpu_weld_shells", "psgpu_weld_shells_device", "psgpu_download_weld_shells", "psgpu_weld_shells_times",
     "psgpu_group_weld_shells", "psgpu_group_weld_shells_device", "psgpu_group_download_weld_shells",
@@ -156,6 +157,8 @@ DEBUG_FRONT_LATE_S1 = 1 << 27
 DEBUG_EPOCH_NEAR_WRAP = 1 << 28  # test hook: the next run starts 3 runs short of the epoch's wrap
 DEBUG_EXPORT_POISON = 1 << 23  # test hooks of the blocking export (OPT_DEBUG bits)
 DEBUG_EXPORT_STRAGGLER = 1 << 24
+DEBUG_S2_ALL_OCTANTS = 1 << 7  # S2 treats every octant as undecided: two passes, all 512 corners (ablation)
+DEBUG_S2_COUNT_PASSES = 1 << 9  # S2 counts the passes it walks (s2_passes())
 DEBUG_BRICK_SPREAD = 1 << 14  # k_precheck's wave W takes brick (W * brickStride) mod bricks (bench.py --debug)
 JIT_INTERP, JIT_STRUCTURE, JIT_BAKED, JIT_TIERED = 0, 1, 2, 3  # OPT_JIT values
 STAMP_KERNELS = ("k_precheck", "k_mpu", "k_vertex", "k_finish")
@@ -578,6 +581,26 @@ class Polygonizer:
         _check(self._L.psgpu_live_bricks(self._ctx, out.ctypes.data, len(out), ctypes.byref(ct)),
                "psgpu_live_bricks")
         return out[:ct.value]
+
+    def mpu_octants(self) -> np.ndarray:
+        """Debug export of the finished run's S1 octant verdicts per MPU of the range, from its
+        queue entries: bit c: octant c proven outside, bit 8 + c: proven inside; 0 if not queued."""
+        info = self.finish()
+        out = np.zeros(max(info.ctMPUs, 1), np.uint16)
+        fn = self._L.psgpu_mpu_octants  # bound here: PSGPU_AB_LIB may name a library from before it
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32], ctypes.c_int
+        _check(fn(self._ctx, out.ctypes.data, len(out)), "psgpu_mpu_octants")
+        return out[:info.ctMPUs]
+
+    def s2_passes(self) -> int:
+        """Debug export of the finished run's S2 passes (4 undecided octants of one MPU per pass);
+        counted only in a run with DEBUG_S2_COUNT_PASSES in OPT_DEBUG, 0 otherwise."""
+        self.finish()
+        ct = ctypes.c_uint32()
+        fn = self._L.psgpu_s2_passes  # bound here: PSGPU_AB_LIB may name a library from before it
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        _check(fn(self._ctx, ctypes.byref(ct)), "psgpu_s2_passes")
+        return int(ct.value)
 
     def export_polympus(self, capacity: int | None = None) -> np.ndarray:
         info = self.finish()
